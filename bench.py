@@ -31,7 +31,17 @@ synchronize, K timed steps, synchronize + barrier; `value` / `ms_per_step` are w
 The legs outside the timed region (configs[], T1, e2e, cpu_baseline) live in bench_legs.py; this file keeps the launch logic, the
 headline's timed region, the roofline and the result line.
 
-Extra objects of the full record (tier contract; the compact line keeps their numbers):
+Plain run vs --full: a plain `bench.py --gpus N --steps K --warmup W` does only what the headline needs -- set up, spin up, warm up,
+time the K steps, write the outputs if --dump-outputs is given, print the line.  Its `roofline` is the event-timed one of the timed
+region with `traffic` read from the committed PMC summary (as --no-live-pmc did).  The live PMC passes, configs[] (C3/C4/C5, T1,
+prefill; the C5 tp=N entry for N > 1), e2e and cpu_baseline run only with --full, where the --no-* switches below still apply.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step computed -- the hidden state the decode step hands
+back (DecodeStep.out, or the "modules" step's result) -- as DIR/hidden_out.npy in float32.  The inputs are seeded (weights, norms and
+the token embedding from one torch.Generator, seed 1234 + rank), so two builds run with the same arguments can be compared output for
+output.
+
+Extra objects of the full record (tier contract; the compact line keeps their numbers; `--full` only except the event-timed roofline):
   roofline      dominant kernel = gptqhip::skinny1_kernel (round 6: the batch-1 fused dequant-GEMV in its preload form, decode-op
                 instantiation with the layer glue fused; bf16 runs and GPTQHIP_DECODE_BITFAITHFUL=1 use its bit-faithful instantiation);
                 achieved = algorithmic bytes per launch (K*N/2 + G*N*2 + G*N/2 + M*(K+N)*2, averaged over the launches) /
@@ -384,7 +394,14 @@ def main():
     ap.add_argument("--handshake-only", action="store_true",
                     help="launch / rendezvous check only: spawn the ranks, all-reduce ones, print {n_gpus, ranks_seen}; needs no GPU "
                          "(gloo when CUDA is unavailable) -- tests/test_host_logic.py uses it to prove --gpus is honoured")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: live PMC traffic, configs[] (C3/C4/C5, T1, prefill; C5 tp=N for N > 1), "
+                         "e2e and cpu_baseline (each still subject to its --no-* switch); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the hidden state of the last timed step as DIR/hidden_out.npy (float32, rank 0)")
     args = ap.parse_args()
+    if args.dump_outputs and args.model != "llama3-8b":
+        raise SystemExit("bench.py: --dump-outputs is implemented for the llama3-8b headline only")
 
     cmd = spawn_command(args.gpus, os.environ, sys.argv[1:])
     if cmd is not None:
@@ -464,11 +481,12 @@ def main():
         raise SystemExit("bench.py: the decode chain produced non-finite activations; refusing to time garbage")
     del out0
     graph = None
+    last_out = [None]      # the tensor the latest step wrote its result to (--dump-outputs)
     if not args.no_graph:
         with torch.cuda.stream(stream):
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=stream):
-                step.run()
+                last_out[0] = step.run()     # the graph's own output buffer: every replay rewrites it
 
     def run(n):
         with torch.cuda.stream(stream):
@@ -476,7 +494,7 @@ def main():
                 if graph is not None:
                     graph.replay()
                 else:
-                    step.run()
+                    last_out[0] = step.run()
 
     # clock / TLB spin-up before the W warm-up steps of the contract: with the driver's --warmup 5 (6 ms of GPU work) the timed steps ran
     # 2.5 % slower than after 20+ warm-up steps (8.85 vs 8.63 us per launch; the chip ramps its clocks over the first ~25 ms of a
@@ -519,9 +537,15 @@ def main():
     ms_per_step = wall * 1e3 / args.steps
     value = world * args.steps / wall   # replicas add up
 
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "hidden_out.npy"), last_out[0].detach().float().cpu().numpy())
+    last_out[0] = None
+
     used_graph = graph is not None
     tp_entry = None
-    if world > 1 and not args.no_configs:
+    if world > 1 and args.full and not args.no_configs:
         # BASELINE configs[4] on the SAME ranks: the 70B decode step tensor-parallel over all of them (every rank takes part)
         del step, graph
         layers.clear()
@@ -536,7 +560,7 @@ def main():
 
     if rank == 0:
         traffic, traffic_source = (None, "")
-        if not args.no_live_pmc and world == 1 and not os.environ.get("GPTQHIP_BENCH_SHARE_GPU"):
+        if args.full and not args.no_live_pmc and world == 1 and not os.environ.get("GPTQHIP_BENCH_SHARE_GPU"):
             traffic, traffic_source = live_pmc(args.dtype)
         if traffic is None:
             note = traffic_source
@@ -578,7 +602,7 @@ def main():
             out["configs"] = [tp_entry]
         if share:
             out["note"] = "GPTQHIP_BENCH_SHARE_GPU=1: every rank ran on GPU 0 over gloo -- a launch / code-path smoke run, NOT a measurement"
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             from bench_legs import extra_configs
             out["configs"] = extra_configs(args, cfg, layers, dtype, dev, gen, stream, make_step, mode, ms_per_step, n_launch)
             if out["configs"] and out["configs"][-1].get("config") == "_prefill_headline":
@@ -586,7 +610,7 @@ def main():
         layers.clear()
         step = graph = None
         torch.cuda.empty_cache()
-        if world == 1 and not args.no_e2e and not args.no_configs:
+        if world == 1 and args.full and not args.no_e2e and not args.no_configs:
             # the whole model, not just the quantised linears: HF LlamaForCausalLM with Llama-3-8B shapes (random init), real
             # attention / KV cache / norms / lm_head, decode through make_quant -> fuse_siblings -> post_init -- eager
             # generate() and one captured graph per decode step (the reference's speed metric is generate() wall time,
@@ -598,7 +622,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 out["e2e"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from bench_legs import cpu_baseline
             out["cpu_baseline"] = cpu_baseline(cfg, gs)
         emit(out)

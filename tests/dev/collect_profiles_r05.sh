@@ -14,10 +14,10 @@ for d in r05_pmc_fetch r05_pmc_write; do python $R/tests/dev/pmc_agg.py $O/$d > 
 find $O/r05_stats $O/r05_pmc_fetch $O/r05_pmc_write -type f -size +12M -delete 2>/dev/null
 cd $R
 # (3) plain runs: the default command (what the driver records), then the variants
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r05_bench_line.json 2> $O/r05_bench.err
+timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r05_bench_line.json 2> $O/r05_bench.err
 cp $O/bench_detail.json $O/r05_bench_detail.json
-timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-configs --no-e2e > $O/r05_bench_line_200steps.json 2>/dev/null
-timeout 300 python bench.py --dtype bf16 --no-cpu-baseline --no-configs > $O/r05_bench_bf16.json 2>/dev/null
+timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-configs --no-e2e --full > $O/r05_bench_line_200steps.json 2>/dev/null
+timeout 300 python bench.py --dtype bf16 --no-cpu-baseline --no-configs --full > $O/r05_bench_bf16.json 2>/dev/null
 timeout 300 python tests/dev/gemm_tflops.py bf16 2>&1 | grep "^M=" > $O/r05_gemm_tflops_bf16.txt
 timeout 300 python tests/dev/gemm_tflops.py bf16 bf16s 2>&1 | grep "^M=" > $O/r05_gemm_tflops_bf16_bf16scales.txt
 timeout 300 python tests/dev/gemm_tflops.py 2>&1 | grep "^M=" > $O/r05_gemm_tflops.txt

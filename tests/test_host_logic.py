@@ -603,8 +603,15 @@ def test_reference_snapshot_recipe_lists_what_the_shim_executes():
         pytest.skip("no oracle/_ref snapshot on this box (it is made where /root/reference is mounted)")
     for rel in ("gptqmodel/nn_modules/qlinear/torch.py", "gptqmodel/nn_modules/qlinear/torch_awq.py", "SNAPSHOT.txt"):
         assert os.path.isfile(os.path.join(snap, rel)), rel
-    ign = subprocess.run(["git", "check-ignore", "-q", "oracle/_ref/SNAPSHOT.txt"], cwd=root)
-    assert ign.returncode == 0, "oracle/_ref must stay out of the history"
+    # the repository's own .gitignore keeps it out (read directly: a checkout exported without .git must pass this too) ...
+    with open(os.path.join(root, ".gitignore")) as f:
+        rules = {ln.strip() for ln in f}
+    assert rules & {"oracle/_ref/", "/oracle/_ref/", "oracle/_ref", "/oracle/_ref"}, "oracle/_ref must stay out of the history"
+    # ... and, where the checkout is itself a git work tree that git will read, git agrees
+    top = subprocess.run(["git", "rev-parse", "--show-toplevel"], cwd=root, capture_output=True, text=True)
+    if top.returncode == 0 and os.path.realpath(top.stdout.strip()) == os.path.realpath(root):
+        ign = subprocess.run(["git", "check-ignore", "-q", "oracle/_ref/SNAPSHOT.txt"], cwd=root)
+        assert ign.returncode == 0, "oracle/_ref must stay out of the history"
     code = ("import os, sys; sys.path.insert(0, %r); os.environ['GPTQ_REFERENCE_ROOT'] = %r\n"
             "from oracle.ref_import import load_reference, REF_IS_SNAPSHOT\n"
             "r = load_reference(); assert REF_IS_SNAPSHOT and r.TorchLinear.__module__ == 'gptqmodel.nn_modules.qlinear.torch'\n" % (root, snap))
