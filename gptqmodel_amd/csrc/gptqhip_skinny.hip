@@ -529,9 +529,12 @@ __device__ __forceinline__ float wave64_sum(float v) {
 }
 
 // bf16 activations on the RAW-code path (decode form 5): the f16 matrix pipe is the one that takes the codes as denormals, so a wave turns its
-// (glued) bf16 x pieces into fp16 -- exactly: a bf16 value has 8 significant bits -- after dividing them by a power of two chosen from the wave's
-// own largest |x| (so that nothing overflows fp16's 2^15 range whatever the input; elements more than 2^29 below the wave's largest lose bits,
-// their products are below fp32's resolution of the sum anyway).  The power of two goes back in through the chunk constants.
+// (glued) bf16 x pieces into fp16 after dividing them by a power of two 2^k chosen from the wave's own largest |x|, so that the largest lands in
+// [2^14, 2^15): nothing overflows fp16's range, and nothing tiny falls below it -- k goes BOTH ways (a wave of 1e-9's is scaled up by 2^44).  A bf16
+// value has 8 significant bits and fp16 holds 8 bits down to 2^-17 (its denormals reach 2^-24), so the conversion is exact for every element whose
+// exponent is within 31 of the wave's largest; elements more than about 2^31 below the largest lose low bits (truncated toward zero, gone below
+// 2^-39 of it) -- their products are below fp32's resolution of the wave's sum anyway.  A zero (or bf16-denormal) maximum takes k = 0.  The
+// power of two goes back in through the chunk constants, in fp32.
 __device__ __forceinline__ uint32_t wave_max_abs_bf16(const u4_t* g, int n) {       // largest |x| of the wave's pieces, as bf16 bits (sign cleared)
     uint32_t m = 0u;
     for (int q = 0; q < n; ++q) {
@@ -550,9 +553,14 @@ __device__ __forceinline__ uint32_t wave_max_abs_bf16(const u4_t* g, int n) {   
     }
     return m;
 }
-__device__ __forceinline__ int bf16_down_shift(uint32_t max_abs_bits) {              // k >= 0 with |x| 2^-k < 2^15 for every element
-    const int e = (int)(max_abs_bits >> 7) - 127;
-    return e > 14 ? e - 14 : 0;
+// k with 2^14 <= max|x| 2^-k < 2^15, clamped to |k| <= 126 so that 2^k and 2^-k are both normal floats ((127 +- k) << 23); -> dn = 2^-k, up = 2^k
+__device__ __forceinline__ void bf16_wave_scale(uint32_t max_abs_bits, float& dn, float& up) {
+    const int ef = (int)(max_abs_bits >> 7);                  // biased exponent of the largest |x| (<= 255: k <= 114)
+    int k = ef - (127 + 14);
+    k = k < -126 ? -126 : k;
+    k = ef == 0 ? 0 : k;                                      // all zeros (or bf16 denormals): nothing to scale
+    dn = __builtin_bit_cast(float, (uint32_t)(127 - k) << 23);
+    up = __builtin_bit_cast(float, (uint32_t)(127 + k) << 23);
 }
 __device__ __forceinline__ uint32_t bf16pair_to_f16pair(uint32_t u, float dn) {
     const float lo = __builtin_bit_cast(float, u << 16) * dn, hi = __builtin_bit_cast(float, u & 0xffff0000u) * dn;
@@ -1285,9 +1293,8 @@ __global__ __launch_bounds__(1024) void skinny1_kernel(SkinnyParams p) {
     u4_t gg[4];          // the wave's glued x pieces (parked below; XCVT converts them in between)
     auto convert_pieces = [&]() __attribute__((always_inline)) {
         if constexpr (XCVT) {
-            const int k = bf16_down_shift(wave_max_abs_bf16(gg, nq));
-            const float dn = __builtin_bit_cast(float, (uint32_t)(127 - k) << 23);
-            up = __builtin_bit_cast(float, (uint32_t)(127 + k) << 23);
+            float dn;
+            bf16_wave_scale(wave_max_abs_bf16(gg, nq), dn, up);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 if (q < nq) {
@@ -1629,9 +1636,8 @@ __global__ __launch_bounds__(1024) void skinny1p_kernel(SkinnyParams p) {
     float sx[NQ];      // RAW: Sx of chunk wave + (4 q + rq) W (the same for every tile)
     float up = 1.f;    // XCVT: 2^k, the power of two taken out of this wave's x pieces
     if constexpr (XCVT) {
-        const int k = bf16_down_shift(wave_max_abs_bf16(xq, NQ));
-        const float dn = __builtin_bit_cast(float, (uint32_t)(127 - k) << 23);
-        up = __builtin_bit_cast(float, (uint32_t)(127 + k) << 23);
+        float dn;
+        bf16_wave_scale(wave_max_abs_bf16(xq, NQ), dn, up);
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
 #pragma unroll

@@ -184,3 +184,70 @@ def shared_gpu_wait_ms(world: int, default_ms: int = 10000) -> int:
     world 8 vs 56 us at world 2) and an occasional rotation takes seconds -- so the product's 10 s bound, sized for one process
     per GPU, can expire although nothing is lost.  Those tests wait longer instead of failing on the scheduler."""
     return default_ms if world < 4 else max(default_ms, 120000)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Activation dynamic range of the batch-1 decode path (tests/test_gpu_decode_dynamic_range.py on the GPU,
+# tests/test_bf16_wave_scale_model.py on the CPU): the input families, and a numpy statement of the bf16 -> fp16 conversion of
+# decode form 5 (gptqmodel_amd/csrc/gptqhip_skinny.hip: wave_max_abs_bf16 / bf16_wave_scale / bf16pair_to_f16pair)
+# ----------------------------------------------------------------------------------------------------------
+RANGE_UNIFORM = {"bf16": (1e-12, 1e-9, 1e-6, 1e-4, 0.5, 3e3, 1e6), "fp16": (1e-5, 3e-4, 0.5, 3e3)}
+RANGE_STRUCTURED = ("chunk_only", "ramp", "outlier", "zero", "negzero")
+RANGE_FAMILIES = {"bf16": tuple(f"u{s:g}" for s in RANGE_UNIFORM["bf16"]) + RANGE_STRUCTURED,
+                  "fp16": tuple(f"u{s:g}" for s in RANGE_UNIFORM["fp16"]) + ("subnormal",) + RANGE_STRUCTURED}
+
+
+def dynamic_range_rows(act: str, family: str, m: int, k: int, seed: int = 0) -> np.ndarray:
+    """[m, k] float32 activations, exactly representable in `act`, of one input family (k a multiple of 128):
+      u<s>        randn * s (fp16: clipped to +-65504)
+      subnormal   fp16 only: n * 2^-24 with integer n uniform in [-1023, 1023] -- every element an fp16 subnormal (or 0)
+      chunk_only  non-zero in ONE 128-row chunk only, tiny there (bf16: randn * 1e-7, fp16: subnormals), exact zeros elsewhere
+      ramp        chunk c scaled by 2^-c, floored at 2^-40 (bf16) / 2^-24 (fp16): neighbouring waves see different magnitudes
+      outlier     one large element (bf16 2e5, fp16 6e4), everything else tiny (bf16 randn * 1e-6, fp16 subnormals)
+      zero        +0.0 everywhere;  negzero: -0.0 everywhere"""
+    assert k % 128 == 0 and family in RANGE_FAMILIES[act], (act, family, k)
+    rng = np.random.RandomState(9000 + seed)
+    sub = lambda: rng.randint(-1023, 1024, size=(m, k)).astype(np.float32) * np.float32(2.0 ** -24)   # noqa: E731
+    tiny = (lambda: rng.randn(m, k).astype(np.float32) * np.float32(1e-6)) if act == "bf16" else sub
+    if family.startswith("u"):
+        x = rng.randn(m, k).astype(np.float32) * np.float32(float(family[1:]))
+        if act == "fp16":
+            x = np.clip(x, -65504.0, 65504.0)
+    elif family == "subnormal":
+        x = sub()
+    elif family == "chunk_only":
+        x = np.zeros((m, k), np.float32)
+        c = 5 % (k // 128)
+        x[:, 128 * c:128 * (c + 1)] = (rng.randn(m, k).astype(np.float32) * np.float32(1e-7) if act == "bf16" else sub())[:, :128]
+    elif family == "ramp":
+        floor = -40 if act == "bf16" else -24
+        e = np.maximum(-(np.arange(k) // 128), floor).astype(np.float64)
+        x = (rng.randn(m, k) * 0.5 * 2.0 ** e[None, :]).astype(np.float32)
+    elif family == "outlier":
+        x = tiny()
+        x[:, 7] = 2.0e5 if act == "bf16" else 6.0e4
+    else:
+        x = np.full((m, k), 0.0 if family == "zero" else -0.0, np.float32)
+    return O.round_to(x, act)
+
+
+def np_bf16_wave_to_f16(x_bf16_as_f32: np.ndarray, groups, down_only: bool = False):
+    """What a wave of decode form 5 is meant to do with its bf16 x pieces, in numpy.  `x_bf16_as_f32`: [K] float32 holding bf16 values;
+    `groups`: the number of consecutive elements that share one wave (an int dividing K) or an int array [K] of group ids.
+    Per group: take the maximum of |x|, choose the integer k that puts it in [2^14, 2^15) -- clamped to |k| <= 126, k = 0 when the maximum is
+    zero or a bf16 subnormal --, multiply by 2^-k, convert to fp16 with round-toward-zero.  -> (fp16 values [K], 2^k per element [K] float64);
+    x is recovered as f16.astype(float64) * up.  down_only=True models the scheme this one replaces (k = max(k, 0): never scaled up)."""
+    x = np.asarray(x_bf16_as_f32, np.float32).reshape(-1)
+    gid = np.arange(x.size) // int(groups) if np.isscalar(groups) else np.asarray(groups).reshape(-1)
+    k = np.zeros(x.size, np.int64)
+    for g in np.unique(gid):
+        sel = gid == g
+        ef = int((np.abs(x[sel]).max().view(np.uint32) >> 23) & 0xFF)          # biased exponent of the group's largest |x|
+        kg = 0 if ef == 0 else max(ef - (127 + 14), -126)
+        k[sel] = max(kg, 0) if down_only else kg
+    y = x.astype(np.float64) * 2.0 ** (-k).astype(np.float64)                   # exact: a power of two, far inside float64's range
+    _, e = np.frexp(y)                                                          # |y| = m 2^e with m in [0.5, 1)
+    quantum = 2.0 ** np.maximum(e - 11, -24).astype(np.float64)                 # fp16: 11 significant bits, subnormal spacing 2^-24
+    h = np.trunc(y / quantum) * quantum                                         # round toward zero
+    assert np.abs(h).max(initial=0.0) < 65536.0
+    return h.astype(np.float16), 2.0 ** k.astype(np.float64)

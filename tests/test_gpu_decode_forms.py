@@ -231,7 +231,7 @@ def test_raw_code_form_adversarial_inputs(ops, case):
 
 
 @pytest.mark.parametrize("K,N,sdt", [(4096, 4096, "bf16"), (14336, 4096, "bf16"), (4096, 6144, "fp16")])
-@pytest.mark.parametrize("xscale", [0.5, 3000.0, 1e-3])
+@pytest.mark.parametrize("xscale", [0.5, 3000.0, 1e-3, 1e-6, 1e-9])
 def test_bf16_raw_code_form_vs_exact_arithmetic(ops, K, N, sdt, xscale):
     """Form 5 on bf16 activations: the wave converts its bf16 x pieces to fp16 exactly (divided by a power of two taken from its largest |x|) and
     runs the raw-code path of the f16 matrix pipe; the output is the bf16 rounding of the exact sum.  Against float64 arithmetic on the integer
