@@ -11,6 +11,15 @@ namespace gptqhip {
 // dequant: thread (r, n) unpacks one packed word and writes pf rows of column n (coalesced over n).
 // Reference: torch.py:700-717 (_dequantize_weight_cached_248) == qlinear/__init__.py:1001-1003.
 // ---------------------------------------------------------------------------------------------
+// s * d with IEEE's sign of a zero product.  For fptrunc(fpext(h) * f) hipcc selects v_fma_mixlo_f16 with a +0 addend, and -s * 0 = -0 plus +0
+// is +0: a negative scale on a code equal to its zero-point came out as +0.0 where the reference's fp16 multiply gives -0.0.  An fma with an
+// opaque -0 addend (a literal one is folded back into the bare product) keeps the sign and changes nothing else.
+__device__ __forceinline__ float mul_keep_zero_sign(float s, float d) {
+    float nz = -0.f;
+    asm volatile("" : "+v"(nz));
+    return __builtin_fmaf(s, d, nz);
+}
+
 template <int BITS, int SCL, int OUT>
 __global__ __launch_bounds__(256) void dequant_kernel(const int32_t* __restrict__ qw, const int32_t* __restrict__ qz,
                                                       const uint16_t* __restrict__ scales,
@@ -31,7 +40,7 @@ __global__ __launch_bounds__(256) void dequant_kernel(const int32_t* __restrict_
         const int zero = (int)((zw >> (BITS * (n % PF))) & MASK);
         const int code = (int)((w >> (BITS * j)) & MASK);
         const float s = load16_as_f32<SCL>(scales, (size_t)g * N + n);
-        float v = round_through<SCL>(s * (float)(code - zero));  // exact product, one rounding
+        float v = round_through<SCL>(mul_keep_zero_sign(s, (float)(code - zero)));  // exact product, one rounding
         out[(size_t)k * N + n] = f32_to_16<OUT>(v);
     }
 }
@@ -329,7 +338,7 @@ __global__ __launch_bounds__(256) void dequant_tiled_kernel(const uint32_t* __re
         const int zero = (int)((mw >> 16) & 0x3FFu);  // 0xE400|z -> low 10 bits hold z
         const int code = (int)((w >> (BITS == 4 ? tiled_shift4(e) : tiled_shift8(e))) & MASK);
         const float s = bits16_to_f32<SCL>((uint16_t)(mw & 0xffffu));
-        const float v = round_through<SCL>(s * (float)(code - zero));
+        const float v = round_through<SCL>(mul_keep_zero_sign(s, (float)(code - zero)));
         const int row = perm ? perm[k] : k;
         out[(size_t)row * N + n] = f32_to_16<OUT>(v);
     }
@@ -671,7 +680,7 @@ __global__ __launch_bounds__(256) void embedding_kernel(const int64_t* __restric
     const uint32_t mw = meta[((size_t)tile * G + k / group_size) * 16 + c];
     const int zero = (int)((mw >> 16) & 0x3FFu);
     const float s = bits16_to_f32<SCL>((uint16_t)(mw & 0xffffu));
-    out[(size_t)t * N + n] = f32_to_16<SCL>(s * (float)((int)code - zero));  // exact product, one rounding
+    out[(size_t)t * N + n] = f32_to_16<SCL>(mul_keep_zero_sign(s, (float)((int)code - zero)));  // exact product, one rounding
 }
 
 int launch_embedding(const int64_t* ids, const uint32_t* qw, const uint32_t* meta, const int32_t* inv_perm, void* out,

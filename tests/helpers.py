@@ -251,3 +251,172 @@ def np_bf16_wave_to_f16(x_bf16_as_f32: np.ndarray, groups, down_only: bool = Fal
     h = np.trunc(y / quantum) * quantum                                         # round toward zero
     assert np.abs(h).max(initial=0.0) < 65536.0
     return h.astype(np.float16), 2.0 ** k.astype(np.float64)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Weight-side dynamic range (tests/test_weight_range_families_cpu.py on the CPU, tests/test_gpu_weight_dynamic_range.py on the GPU):
+# scales from fp16 subnormals to the largest the reference's fp16 weights stay finite with, exponents that differ between neighbouring
+# groups / columns, negative and zero scales; codes that cluster around the zero-point (what a trained checkpoint holds), sit on it, or
+# sit at the ends of the code range.  synth_gptq above draws scales in [0.005, 0.015] and uniform codes only.
+# ----------------------------------------------------------------------------------------------------------
+WEIGHT_SCALE_STRUCTURED = ("group_ramp", "column_ramp", "outlier_group", "signed", "zero_groups")
+WEIGHT_CODE_FAMILIES = ("random", "near_zero_point", "at_zero_point", "extremes", "sym")
+WEIGHT_RANGE_FAMILIES = {"scale": ("sub", "u<m>") + WEIGHT_SCALE_STRUCTURED, "code": WEIGHT_CODE_FAMILIES}
+
+
+def weight_scale_top(bits: int) -> float:
+    """The largest ladder step m: (2^bits - 1) * 2 m -- the largest |s (q - z)| of a u<m> layer -- is still finite in fp16."""
+    return {4: 2048.0, 8: 64.0}[bits]
+
+
+def weight_scale_ladder(act: str, scale_dtype: str, bits: int):
+    """The steps m of the u<m> families: from the smallest normal of the scale dtype's useful range to the top.  fp16 scales start at
+    2^-14; bf16 scales at 2^-60 with bf16 activations and at 2^-24 with fp16 activations (below, every weight the reference casts to
+    fp16 is 0 or one fp16 quantum and no fp16 row can bring the output into fp16's normal range).  With fp16 activations -- and with fp16
+    scales -- the top is weight_scale_top (the reference's own rounded weights stay finite); bf16 x bf16 goes on to 2^60."""
+    top = weight_scale_top(bits)
+    if scale_dtype == "fp16":
+        return (2.0 ** -14, 1e-3, 0.01, 1.0, top)
+    if act == "fp16":
+        return (2.0 ** -24, 2.0 ** -14, 1e-3, 0.01, 1.0, top)
+    return (2.0 ** -60, 2.0 ** -14, 1e-3, 0.01, 1.0, top, 2.0 ** 60)
+
+
+def _ladder_name(m: float) -> str:
+    e = int(np.round(np.log2(m)))
+    return f"u2^{e}" if (2.0 ** e == m and abs(e) > 12) else f"u{m:g}"
+
+
+def _ladder_value(name: str) -> float:
+    return 2.0 ** int(name[3:]) if name.startswith("u2^") else float(name[1:])
+
+
+def weight_scale_families(act: str, scale_dtype: str, bits: int):
+    """Names of every scale family of one (activation dtype, scale dtype, bit width): 'sub' (fp16 scales only), the u<m> ladder
+    ('u2^-14', 'u0.001', ..), and the structured ones."""
+    return (("sub",) if scale_dtype == "fp16" else ()) + tuple(_ladder_name(m) for m in weight_scale_ladder(act, scale_dtype, bits)) \
+        + WEIGHT_SCALE_STRUCTURED
+
+
+def weight_range_layer(scale_family, code_family, bits, K, N, gs, scale_dtype, desc_act=False, seed=0):
+    """-> (qweight, qzeros, scales, g_idx), the contract of synth_gptq (numpy legacy RandomState; scales float32, exactly representable
+    in scale_dtype).  Scale families, [G, N], each rounded to scale_dtype:
+      sub            fp16 only: n * 2^-24, n uniform in 1..1023 -- every scale an fp16 subnormal
+      u<m>           m * (1 + rand)                                    (u2^-14, u0.001, u1, u2048, ..: weight_scale_ladder)
+      group_ramp     u0.01 with group g multiplied by 2^((7 g) mod 21 - 10) = 2^-10, 2^-3, 2^4, 2^-10, ..: neighbouring groups of a column 2^7 / 2^14 apart
+      column_ramp    u0.01 with column n multiplied by 2^((n mod 16) - 8): the 16 lanes of a column tile carry different exponents
+      outlier_group  u2^-20 except ONE group per column at weight_scale_top(bits) * (1 + rand)
+      signed         u0.01 with a random sign per (group, column)
+      zero_groups    u0.01 with about a quarter of the (group, column) scales exactly +0.0 or -0.0
+    Code families (zero-points z [G, N], codes [K, N]):
+      random           uniform codes and zero-points
+      near_zero_point  z uniform, every code in {z - 1, z, z + 1} clipped to the code range
+      at_zero_point    z uniform, every code equal to its z: every weight is exactly 0.  (With zero_groups the groups whose scale IS zero
+                       keep uniform codes -- 0 * anything -- so the layer still dequantises to zeros only.)
+      extremes         z in {0, max}, codes in {0, max}
+      sym              z = 2^(bits - 1), uniform codes"""
+    assert code_family in WEIGHT_CODE_FAMILIES and K % gs == 0, (code_family, K, gs)
+    rng = np.random.RandomState(7000 + seed)
+    G, maxq = K // gs, (1 << bits) - 1
+    g_idx = ((rng.permutation(K) if desc_act else np.arange(K)) // gs).astype(np.int32)
+    u = lambda m: m * (1.0 + rng.rand(G, N))   # noqa: E731
+    if scale_family == "sub":
+        assert scale_dtype == "fp16"
+        s = rng.randint(1, 1024, size=(G, N)).astype(np.float64) * 2.0 ** -24
+    elif scale_family.startswith("u"):
+        s = u(_ladder_value(scale_family))
+    elif scale_family == "group_ramp":
+        s = u(0.01) * 2.0 ** (((7 * np.arange(G)) % 21) - 10.0)[:, None]
+    elif scale_family == "column_ramp":
+        s = u(0.01) * 2.0 ** ((np.arange(N) % 16) - 8.0)[None, :]
+    elif scale_family == "outlier_group":
+        s = u(2.0 ** -20)
+        s[rng.randint(0, G, size=N), np.arange(N)] = weight_scale_top(bits) * (1.0 + rng.rand(N))
+    elif scale_family == "signed":
+        s = u(0.01) * rng.choice([-1.0, 1.0], size=(G, N))
+    elif scale_family == "zero_groups":
+        s = u(0.01)
+        s = np.where(rng.rand(G, N) < 0.25, np.where(rng.rand(G, N) < 0.5, 0.0, -0.0), s)
+    else:
+        raise ValueError(scale_family)
+    scales = O.round_to(s.astype(np.float32), scale_dtype)
+    if code_family == "sym":
+        z = np.full((G, N), 1 << (bits - 1), np.int64)
+    elif code_family == "extremes":
+        z = rng.randint(0, 2, size=(G, N)) * maxq
+    else:
+        z = rng.randint(0, maxq + 1, size=(G, N))
+    zk = z[g_idx]
+    if code_family in ("random", "sym"):
+        codes = rng.randint(0, maxq + 1, size=(K, N))
+    elif code_family == "near_zero_point":
+        codes = np.clip(zk + rng.randint(-1, 2, size=(K, N)), 0, maxq)
+    elif code_family == "at_zero_point":
+        codes = np.where(scales[g_idx] == 0.0, rng.randint(0, maxq + 1, size=(K, N)), zk)
+    else:
+        codes = rng.randint(0, 2, size=(K, N)) * maxq
+    return O.pack_rows(codes.astype(np.uint8), bits), O.pack_cols(z.astype(np.uint8), bits), scales, g_idx
+
+
+def weight_exact_f64(qweight, qzeros, scales, g_idx, bits):
+    """s (q - z) in float64 on the integer codes: [K, N]."""
+    g = O.normalize_g_idx(g_idx, scales.shape[0])
+    return np.asarray(scales, np.float64)[g] * (O.unpack_rows(qweight, bits).astype(np.int64) - O.unpack_cols(qzeros, bits).astype(np.int64)[g])
+
+
+def weight_range_rows(act: str, w_exact: np.ndarray, m: int, seed: int = 0) -> np.ndarray:
+    """[m, K] float32 activations, exactly representable in `act`: randn rows times a power of two per row, chosen from the float64
+    product so that the row's largest |x @ w_exact| lands in [1, 64] (aimed at 8), and clipped so that the row stays inside the
+    activation dtype's normal range (fp16: 2^-10 .. 2^12, i.e. |x| < 65504 and a typical element normal; bf16: 2^+-100).  All waves of a
+    row see one magnitude.  An all-zero product (at_zero_point) keeps the plain randn row."""
+    rng = np.random.RandomState(9100 + seed)
+    x0 = O.round_to(rng.randn(m, w_exact.shape[0]).astype(np.float32), act)
+    y0 = np.abs(x0.astype(np.float64) @ w_exact).max(axis=1)
+    e = np.where(y0 > 0.0, np.rint(np.log2(8.0 / np.where(y0 > 0.0, y0, 1.0))), 0.0)
+    lo, hi = (-10.0, 12.0) if act == "fp16" else (-100.0, 100.0)
+    return O.round_to((x0.astype(np.float64) * 2.0 ** np.clip(e, lo, hi)[:, None]).astype(np.float32), act)
+
+
+# The cases of tests/test_gpu_weight_dynamic_range.py, shared with the CPU test that vouches for them (finite reference weights and
+# outputs, every row's largest |y_exact| in [2^-10, 6e4]).  Shapes: the smallest at which each code path exists.
+WEIGHT_RANGE_DTYPES = (("fp16", "fp16"), ("bf16", "bf16"), ("fp16", "bf16"))             # (activations, scales)
+WEIGHT_RANGE_MAIN = "512x256g128"
+WEIGHT_RANGE_DECODE_SHAPES = {                                                            # name -> (bits, K, N, gs, act-order)
+    "512x256g128": (4, 512, 256, 128, False),
+    "512x256g32": (4, 512, 256, 32, False),            # four group constants per chunk
+    "1408x256g64": (4, 1408, 256, 64, False),          # padded last ring round
+    "512x8192g128": (4, 512, 8192, 128, False),        # two column tiles per CU: the wide forms at 2..16 rows
+    "2048x8192g128": (4, 2048, 8192, 128, False),      # ... with 16 chunks of K: the persistent-tile kernel at one row, the 4-deep ring at 2..4
+    "512x256g128-actorder": (4, 512, 256, 128, True),  # act-order through gptqhip_gemm (x gathered in front of the kernel; the decode op declines it)
+    "2048x1024g128-actorder": (4, 2048, 1024, 128, True),  # ... and the smallest layer the in-kernel permutation serves (the 4-deep ring)
+}
+WEIGHT_RANGE_TILED = {                                   # name -> (bits, K, N, gs, M, set_tuning arguments)
+    "tiled-384x264g128": (4, 384, 264, 128, 70, (0, 2, 0)),
+    "tiled-256x136g64": (4, 256, 136, 64, 33, (0, 2, 0)),
+    "tiled8-256x128g64": (8, 256, 128, 64, 77, (0, 2, 0)),
+    "tiled-n128-384x264g128": (4, 384, 264, 128, 65, (1, 2, 1000 + 64)),
+    "tiled-splitk-384x264g128": (4, 384, 264, 128, 70, (3, 2, 0)),
+}
+WEIGHT_RANGE_MAIN_ROWS = 48                              # 1..16 rows through the decode op, 24 and 48 through gptqhip_gemm
+
+
+def weight_range_side_families(scale_dtype: str):
+    """(scale family, code family) pairs every shape but the main one takes."""
+    return ((("sub", "random"),) if scale_dtype == "fp16" else ()) + (("group_ramp", "random"), ("outlier_group", "random"), ("u0.01", "near_zero_point"))
+
+
+def weight_range_main_families(act: str, scale_dtype: str, bits: int = 4):
+    """... and the main shape: every scale family on uniform codes, every code family (but at_zero_point: its own tests) on u0.01."""
+    return tuple((s, "random") for s in weight_scale_families(act, scale_dtype, bits)) + \
+        tuple(("u0.01", c) for c in ("near_zero_point", "extremes", "sym"))
+
+
+def weight_range_layer_of(shape: str, scale_family: str, code_family: str, scale_dtype: str):
+    """-> (bits, K, N, gs, rows, (qweight, qzeros, scales, g_idx)) of one named case (the seed follows from the shape)."""
+    if shape in WEIGHT_RANGE_DECODE_SHAPES:
+        bits, K, N, gs, desc = WEIGHT_RANGE_DECODE_SHAPES[shape]
+        rows = WEIGHT_RANGE_MAIN_ROWS if shape == WEIGHT_RANGE_MAIN else (1 if desc else (4 if shape == "2048x8192g128" else 16))
+    else:
+        bits, K, N, gs, rows, _ = WEIGHT_RANGE_TILED[shape]
+        desc = False
+    return bits, K, N, gs, rows, weight_range_layer(scale_family, code_family, bits, K, N, gs, scale_dtype, desc_act=desc, seed=K // 32 + N // 8 + gs + bits)
