@@ -1,0 +1,230 @@
+"""HipMoeExperts: the experts of a sparse mixture-of-experts block on the fused MoE decode ops.
+
+GPTQModel quantises MoE checkpoints per expert (three GPTQ linears each) and leaves the execution to the HF modeling code: a host-routed
+loop (one_hot + nonzero() / where() on the router output, i.e. a device-to-host sync per layer) with three QuantLinear.forward calls and an
+index_add_ per active expert.  This module holds ALL experts' tiled words / constants stacked in two buffers per projection and serves the
+call signature of transformers' experts modules (Qwen3MoeExperts.forward / MixtralExperts.forward):
+
+    forward(hidden_states [T, H], top_k_index [T, k], top_k_weights [T, k]) -> [T, H]
+
+* fast path (ops.moe_supported: 4 bits, group_size = 128 * 2^n, no act-order, T <= 16, top_k <= 16): gptqhip_moe_gate_up + gptqhip_moe_down,
+  two launches into persistent buffers with the routing left on the device -- no host synchronisation, safe inside torch.cuda.graph.  An
+  expert id outside [0, E) contributes zero and sets a device status word, which check_status() reads (never forward()).
+  Rounding: per-weight rounding and the SiLU chain are the reference's; the top_k expert outputs are combined in ONE fp32 weighted sum in
+  slot order and rounded once (include/gptqhip.h), where the HF loop rounds every expert's output and every product and accumulates in the
+  activation dtype.
+* slow path (more tokens, other shapes): the host-routed per-expert loop of the HF module on ops.gemm over views into the same stacked
+  buffers -- arithmetically what a loop over the original modules does.
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Sequence, Tuple
+
+import torch
+import torch.nn as nn
+
+from .. import _lib, ops
+from ..utils.model import deinterleave_gate_up, fuse_gate_up_interleaved
+
+MAX_FAST_TOKENS = 16
+
+
+def _interleave_tiled(gate: torch.Tensor, up: torch.Tensor, tiles: int, inner: int, per_lane: int) -> torch.Tensor:
+    """Column-interleave two TILED arrays in blocks of 8 (what fuse_gate_up_interleaved + post_init produce from the checkpoint layout):
+    fused tile 2 t + h takes columns 8 h .. 8 h + 7 of gate tile t as its columns 0 .. 7 and those of up tile t as 8 .. 15.
+    words: [tile][chunk][rq][c][j] -> inner = chunks * 4, per_lane = 4; meta: [tile][group][c] -> inner = groups, per_lane = 1."""
+    g = gate.view(tiles, inner, 2, 8, per_lane)
+    u = up.view(tiles, inner, 2, 8, per_lane)
+    out = torch.empty((tiles, 2, inner, 2, 8, per_lane), dtype=gate.dtype, device=gate.device)
+    out[:, :, :, 0] = g.permute(0, 2, 1, 3, 4)
+    out[:, :, :, 1] = u.permute(0, 2, 1, 3, 4)
+    return out.view(-1)
+
+
+def _is_hip_gptq(m) -> bool:
+    return getattr(m, "_GPTQHIP_KERNEL_CLASS", False) and getattr(m, "QUANT_TYPE", "") == "hip_gptq"
+
+
+def _release(m) -> None:
+    """Drop a per-expert module's device tensors once they are stacked."""
+    for name in ("qweight", "qzeros", "scales", "g_idx", "meta"):
+        t = getattr(m, name, None)
+        if isinstance(t, torch.Tensor):
+            t.data = torch.empty(0, dtype=t.dtype, device=t.device)
+    m._ready = False
+
+
+class HipMoeExperts(nn.Module):
+    def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, gate_up_group_size: int, down_group_size: int,
+                 scale_dtype: torch.dtype):
+        super().__init__()
+        self.num_experts = num_experts
+        self.hidden_dim = hidden_dim
+        self.intermediate_dim = intermediate_dim
+        self.gate_up_group_size = gate_up_group_size
+        self.down_group_size = down_group_size
+        self.scale_dtype = scale_dtype
+        self.bits = 4
+        self.training = False
+        self._scratch: Dict[Tuple, Tuple[torch.Tensor, ...]] = {}
+        self._fast_ok: Dict[Tuple[int, int], bool] = {}
+
+    def train(self, mode: bool = True):
+        if mode:      # the quantised linears it is built from refuse training mode the same way (SUPPORTS_TRAINING = False)
+            raise NotImplementedError("HipMoeExperts: inference only (the HIP quant kernels have no backward)")
+        return super().train(False)
+
+    def extra_repr(self) -> str:
+        return (f"experts={self.num_experts}, hidden={self.hidden_dim}, intermediate={self.intermediate_dim}, bits=4, "
+                f"group_size={self.gate_up_group_size}/{self.down_group_size}")
+
+    # ---------------------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_linears(cls, gate: Sequence[nn.Module], up: Sequence[nn.Module], down: Sequence[nn.Module]) -> "HipMoeExperts":
+        """Three equal-length lists of HIP GPTQ linears (expert e = gate[e], up[e], down[e]) on the ROCm device, either already
+        post_init()ed (tile-major) or still in the checkpoint layout (then post_init() runs here).  gate | up are fused per expert with
+        the column interleave of fuse_gate_up_interleaved, all experts are stacked into two contiguous buffers per projection, and the
+        per-expert copies are released as they are stacked (peak extra memory: one expert).  Raises NotImplementedError when the experts
+        cannot share the stacked layout; nothing has been modified then."""
+        gate, up, down = list(gate), list(up), list(down)
+        E = len(gate)
+        if E == 0 or len(up) != E or len(down) != E:
+            raise NotImplementedError("from_linears needs three equal-length, non-empty lists")
+        g0, d0 = gate[0], down[0]
+        H, I = g0.in_features, g0.out_features
+        for e in range(E):
+            for m, (k, n) in ((gate[e], (H, I)), (up[e], (H, I)), (down[e], (I, H))):
+                if not _is_hip_gptq(m):
+                    raise NotImplementedError(f"expert {e}: {type(m).__name__} is not a HIP GPTQ linear")
+                if getattr(m, "adapter", None) is not None or m.bias is not None:
+                    raise NotImplementedError(f"expert {e}: adapters / biases are not carried by the stacked experts")
+                if (m.in_features, m.out_features) != (k, n):
+                    raise NotImplementedError(f"expert {e}: shape {(m.in_features, m.out_features)} != {(k, n)}")
+                if m.bits != 4 or getattr(m, "planar", False):
+                    raise NotImplementedError(f"expert {e}: {m.bits}-bit codes (4-bit only)")
+                if m.scales.dtype != g0.scales.dtype or m.group_size != (g0 if k == H else d0).group_size or m._ready != g0._ready:
+                    raise NotImplementedError(f"expert {e}: group size / scale dtype / layout differ from expert 0")
+                if not m.qweight.is_cuda:
+                    raise NotImplementedError("buffers must be on the ROCm device")
+                if m._ready:
+                    if m.perm is not None:
+                        raise NotImplementedError(f"expert {e}: act-order")
+                else:
+                    gi = getattr(m, "g_idx", None)
+                    if gi is not None and gi.numel() == k and not torch.equal(
+                            gi.long(), torch.arange(k, device=gi.device, dtype=torch.int64) // m.group_size):
+                        raise NotImplementedError(f"expert {e}: act-order")
+        if I % 16 != 0 or H % 16 != 0:
+            raise NotImplementedError("hidden and intermediate sizes must be multiples of 16")
+        self = cls(E, H, I, g0.group_size, d0.group_size, g0.scales.dtype)
+        dev = g0.qweight.device
+        lib = _lib.load()
+        sizes = [(lib.gptqhip_tiled_words(H, 2 * I, 4), lib.gptqhip_meta_words(H, 2 * I, g0.group_size)),
+                 (lib.gptqhip_tiled_words(I, H, 4), lib.gptqhip_meta_words(I, H, d0.group_size))]
+        bufs = [torch.empty((E, n), dtype=torch.int32, device=dev) for pair in sizes for n in pair]
+        chunks_h = -(-H // 128)
+        ready = g0._ready
+        for e in range(E):
+            if ready:
+                bufs[0][e] = _interleave_tiled(gate[e].qweight.data, up[e].qweight.data, I // 16, chunks_h * 4, 4)
+                bufs[1][e] = _interleave_tiled(gate[e].meta, up[e].meta, I // 16, H // g0.group_size, 1)
+            else:
+                gu = fuse_gate_up_interleaved(gate[e], up[e])
+                gu.post_init()
+                bufs[0][e], bufs[1][e] = gu.qweight.data, gu.meta
+                del gu
+                down[e].post_init()
+            bufs[2][e], bufs[3][e] = down[e].qweight.data, down[e].meta
+            for m in (gate[e], up[e], down[e]):
+                _release(m)
+        for name, t in zip(("gate_up_qweight", "gate_up_meta", "down_qweight", "down_meta"), bufs):
+            self.register_buffer(name, t, persistent=False)
+        self.register_buffer("status", torch.zeros(1, dtype=torch.int32, device=dev), persistent=False)
+        return self
+
+    # ---------------------------------------------------------------------------------------------------------------------------
+    def fast_path(self, T: int, top_k: int, dtype: torch.dtype) -> bool:
+        """Whether forward() serves this call with the two fused launches."""
+        key = (T, top_k)
+        ok = self._fast_ok.get(key)
+        if ok is None:
+            gs = self.gate_up_group_size
+            if gs != self.down_group_size:      # one group for the whole K of each projection (group_size = -1), or not servable
+                gs = -1 if (gs == self.hidden_dim and self.down_group_size == self.intermediate_dim) else 0
+            ok = gs != 0 and ops.moe_supported(self.hidden_dim, self.intermediate_dim, gs, self.bits, False, T, top_k)
+            self._fast_ok[key] = ok
+        return ok and dtype in (torch.float16, torch.bfloat16) and not (dtype == torch.bfloat16 and self.scale_dtype == torch.float16)
+
+    def _scratch_for(self, T: int, top_k: int, dtype: torch.dtype, device: torch.device):
+        key = (T, top_k, dtype)
+        s = self._scratch.get(key)
+        if s is None or s[0].device != device:
+            s = (torch.empty((T * top_k, self.intermediate_dim), dtype=dtype, device=device),
+                 torch.empty((T, self.hidden_dim), dtype=dtype, device=device),
+                 torch.empty((T, top_k), dtype=torch.int32, device=device),
+                 torch.empty((T, top_k), dtype=torch.float32, device=device))
+            self._scratch[key] = s
+        return s
+
+    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
+        if hidden_states.dim() != 2 or hidden_states.shape[1] != self.hidden_dim or top_k_index.dim() != 2 \
+                or top_k_index.shape != top_k_weights.shape or top_k_index.shape[0] != hidden_states.shape[0]:
+            raise RuntimeError(f"HipMoeExperts: expected hidden_states [T, {self.hidden_dim}] and top_k_index / top_k_weights [T, k], got "
+                               f"{tuple(hidden_states.shape)}, {tuple(top_k_index.shape)}, {tuple(top_k_weights.shape)}")
+        if not hidden_states.is_cuda:
+            raise RuntimeError("gptqmodel_amd HIP ops need tensors on a ROCm device (got a CPU tensor); there is no CPU fallback")
+        T, top_k = top_k_index.shape
+        if T == 0:
+            return torch.zeros_like(hidden_states)
+        if T > MAX_FAST_TOKENS or not self.fast_path(T, top_k, hidden_states.dtype):
+            return self._forward_loop(hidden_states, top_k_index, top_k_weights)
+        # the result lives in a persistent buffer of this module (one per (T, top_k, dtype)): the next call with that signature overwrites it
+        act, out, ids, w = self._scratch_for(T, top_k, hidden_states.dtype, hidden_states.device)
+        if top_k_index.dtype == torch.int32 and top_k_index.is_contiguous():
+            ids = top_k_index
+        else:
+            ids.copy_(top_k_index)
+        if top_k_weights.dtype == torch.float32 and top_k_weights.is_contiguous():
+            w = top_k_weights
+        else:
+            w.copy_(top_k_weights)
+        x = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
+        ops.moe_gate_up(x, self.gate_up_qweight, self.gate_up_meta, ids, act, self.status, self.num_experts, self.intermediate_dim,
+                        self.gate_up_group_size, self.scale_dtype)
+        ops.moe_down(act, self.down_qweight, self.down_meta, ids, w, out, self.status, self.num_experts, self.down_group_size,
+                     self.scale_dtype)
+        return out
+
+    def check_status(self) -> None:
+        """Host read of the device status word (a synchronisation: call it outside the decode loop).  Raises IndexError when a fast-path
+        call since the last check met an expert id outside [0, num_experts) -- that slot contributed zero -- and clears the word."""
+        if int(self.status.item()) != 0:
+            self.status.zero_()
+            raise IndexError(f"HipMoeExperts: expert index out of range [0, {self.num_experts}) in a fused MoE call")
+
+    def _forward_loop(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
+        """The experts loop of the HF module (host-routed) on ops.gemm over views into the stacked buffers."""
+        x = hidden_states
+        in_dtype = x.dtype
+        if in_dtype not in (torch.float16, torch.bfloat16):
+            x = x.to(torch.float16)
+        idx = top_k_index.long()
+        E, I, H = self.num_experts, self.intermediate_dim, self.hidden_dim
+        if bool(((idx < 0) | (idx >= E)).any()):
+            raise IndexError(f"HipMoeExperts: expert index out of range [0, {E})")
+        final = torch.zeros_like(x)
+        mask = torch.nn.functional.one_hot(idx, num_classes=E).permute(2, 1, 0)
+        for e in torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero().flatten().tolist():
+            pos, tok = torch.where(mask[e])
+            cur = x[tok].contiguous()
+            gu = ops.gemm(cur, self.gate_up_qweight[e], self.gate_up_meta[e], None, None, 2 * I, self.gate_up_group_size, self.bits,
+                          self.scale_dtype)
+            g, u = deinterleave_gate_up(gu)
+            h = (torch.nn.functional.silu(g) * u).contiguous()
+            d = ops.gemm(h, self.down_qweight[e], self.down_meta[e], None, None, H, self.down_group_size, self.bits, self.scale_dtype)
+            d = d * top_k_weights[tok, pos, None]
+            final.index_add_(0, tok, d.to(final.dtype))
+        return final if final.dtype == in_dtype else final.to(in_dtype)
+
+
+__all__ = ["HipMoeExperts", "MAX_FAST_TOKENS"]

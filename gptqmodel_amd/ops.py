@@ -261,6 +261,62 @@ def decode_linear(x: torch.Tensor, qweight_t: torch.Tensor, meta: torch.Tensor, 
     return out
 
 
+def moe_supported(H: int, I: int, group_size: int, bits: int = 4, has_perm: bool = False, T: int = 1, top_k: int = 1) -> bool:
+    """True when the fused MoE decode ops (gptqhip_moe_gate_up / gptqhip_moe_down) serve experts with hidden size H and intermediate
+    size I for T tokens x top_k slots (host logic, no GPU); group_size <= 0: one group for the whole K of each projection."""
+    return bool(_lib.load().gptqhip_moe_supported(H, I, group_size, bits, 1 if has_perm else 0, T, top_k))
+
+
+def _moe_check(what: str, x: torch.Tensor, rows: int, cols: int, ids: torch.Tensor, status: torch.Tensor, scale_dtype: torch.dtype):
+    if x.dtype not in _DT or scale_dtype not in _DT:
+        raise RuntimeError(f"{what}: unsupported dtypes x={x.dtype} scales={scale_dtype}")
+    if x.dim() != 2 or tuple(x.shape) != (rows, cols) or not x.is_contiguous():
+        raise RuntimeError(f"{what}: input must be a contiguous [{rows}, {cols}] tensor (got {tuple(x.shape)})")
+    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
+        raise RuntimeError(f"{what}: ids must be a contiguous int32 [T, top_k] tensor")
+    if status.dtype != torch.int32 or status.numel() < 1:
+        raise RuntimeError(f"{what}: status must be an int32 tensor")
+
+
+def moe_gate_up(x: torch.Tensor, qweight_t: torch.Tensor, meta: torch.Tensor, ids: torch.Tensor, act: torch.Tensor, status: torch.Tensor,
+                E: int, I: int, group_size: int, scale_dtype: torch.dtype, bits: int = 4) -> torch.Tensor:
+    """Stage one of the fused MoE experts (gptqhip_moe_gate_up): act[t * top_k + j, :I] = silu(g) * u with g | u = x[t] @ the fused, interleaved
+    gate|up projection of expert ids[t, j], read from the stacked tiled words / constants of all E experts.  x [T, H], ids int32 [T, top_k]
+    (on the device: nothing is read back), act [T * top_k, I] and status (int32, set to 1 by an id outside [0, E)) are the caller's."""
+    _require_cuda(x, qweight_t, meta, ids, act, status)
+    T, top_k = ids.shape if ids.dim() == 2 else (0, 0)
+    H = x.shape[-1]
+    _moe_check("moe_gate_up", x, T, H, ids, status, scale_dtype)
+    if act.dtype != x.dtype or act.numel() < T * top_k * I or not act.is_contiguous():
+        raise RuntimeError(f"moe_gate_up: act must be a contiguous {x.dtype} tensor with >= {T * top_k * I} elements")
+    with torch.cuda.device(x.device):
+        rc = _lib.load().gptqhip_moe_gate_up(_ptr(x), _ptr(qweight_t), _ptr(meta), _ptr(ids), _ptr(act), _ptr(status), T, top_k, E, H, I,
+                                             group_size, bits, _DT[x.dtype], _DT[scale_dtype], _stream(x.device))
+    _lib.check(rc, "gptqhip_moe_gate_up")
+    return act
+
+
+def moe_down(act: torch.Tensor, qweight_t: torch.Tensor, meta: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, out: torch.Tensor,
+             status: torch.Tensor, E: int, group_size: int, scale_dtype: torch.dtype, bits: int = 4) -> torch.Tensor:
+    """Stage two (gptqhip_moe_down): out[t, :H] = round( sum_j weights[t, j] * (act[t * top_k + j] @ down projection of expert ids[t, j]) ), fp32
+    dot products and ONE fp32 weighted sum in slot order, rounded once (deterministic: no atomics).  act [T * top_k, I], weights float32
+    [T, top_k], out [T, H]."""
+    _require_cuda(act, qweight_t, meta, ids, weights, out, status)
+    T, top_k = ids.shape if ids.dim() == 2 else (0, 0)
+    I = act.shape[-1]
+    _moe_check("moe_down", act, T * top_k, I, ids, status, scale_dtype)
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (T, top_k) or not weights.is_contiguous():
+        raise RuntimeError("moe_down: weights must be a contiguous float32 [T, top_k] tensor")
+    if out.dtype != act.dtype or out.dim() != 2 or out.shape[0] != T or not out.is_contiguous():
+        raise RuntimeError(f"moe_down: out must be a contiguous {act.dtype} [T, H] tensor")
+    H = out.shape[1]
+    with torch.cuda.device(act.device):
+        rc = _lib.load().gptqhip_moe_down(_ptr(act), _ptr(qweight_t), _ptr(meta), _ptr(ids), _ptr(weights), _ptr(out), _ptr(status), T, top_k, E,
+                                          H, I, group_size, bits, _DT[act.dtype], _DT[scale_dtype], _stream(act.device))
+    _lib.check(rc, "gptqhip_moe_down")
+    return out
+
+
 def dequant(qweight, qzeros, scales, g_idx, group_size: int, bits: int, out_dtype=None) -> torch.Tensor:
     """[K,N] weights from the CHECKPOINT layout (bit-exact with the reference's dequantize_weight())."""
     lib = _lib.load()

@@ -454,6 +454,14 @@ def auto_fuse(model: nn.Module) -> int:
         return 0
     if not isinstance(model, nn.Module) or _is_quant(model):
         return 0
+    n = _auto_fuse_layers(model)
+    # sparse mixture-of-experts blocks (their layers were skipped above: no mlp.gate_proj): experts onto the fused MoE decode ops
+    from .moe import auto_fuse_moe
+    auto_fuse_moe(model)
+    return n
+
+
+def _auto_fuse_layers(model: nn.Module) -> int:
     try:
         has_layer = any(all(hasattr(m, a) for a in ("self_attn", "mlp", "input_layernorm", "post_attention_layernorm")) for m in model.modules())
         if not has_layer:

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GPTQHIP_ABI_VERSION 19
+#define GPTQHIP_ABI_VERSION 20
 
 /* error codes */
 #define GPTQHIP_OK 0
@@ -220,6 +220,39 @@ int gptqhip_repack_awq(const int32_t* qweight_awq, const int32_t* qzeros_awq,
 int gptqhip_embedding(const int64_t* ids, const uint32_t* qweight_t, const uint32_t* meta, const int32_t* inv_perm,
                       void* out, int32_t* status, int T, int K, int N, int group_size, int bits, int scale_dtype,
                       gptqhip_stream_t stream);
+
+/* FUSED QUANTISED MIXTURE-OF-EXPERTS DECODE OPS for a few tokens (gptqmodel_amd/csrc/gptqhip_moe.hip).  No reference native is replaced:
+ * GPTQModel quantises MoE checkpoints per expert and leaves their execution to the HF modeling code, so the two ops stand in for the expert
+ * loop of transformers' experts modules (Qwen3MoeExperts.forward / MixtralExperts.forward, modeling_qwen3_moe.py / modeling_mixtral.py: one_hot +
+ * nonzero() / where() on the router output -- a device-to-host sync per layer -- then three QuantLinear.forward calls and an index_add_ per active
+ * expert).  Here the routing stays on the DEVICE and the launch geometry depends only on (T, top_k, shapes): nothing synchronises, the pair can be
+ * captured in a graph.
+ *   Weights: the experts' tiled words / meta constants (gptqhip_repack_tiled) STACKED at a constant stride -- expert e starts at
+ *            qweight_t + e * gptqhip_tiled_words(K, N, 4) and meta + e * gptqhip_meta_words(K, N, group_size), with (K, N) = (H, 2I) for the fused
+ *            gate|up projection, whose columns are interleaved in blocks of 8 (utils.model.fuse_gate_up_interleaved), and (I, H) for down.
+ *   Routing: ids int32 [T, top_k], weights float32 [T, top_k].  An id outside [0, E) dereferences nothing: the slot contributes zero and the device
+ *            int32 `status` word is set to 1 (the convention of gptqhip_embedding); the caller zeroes it and reads it when it chooses to.
+ *   gptqhip_moe_gate_up   act[s, :I] = act(act(silu(act(g))) * act(u)),  g | u = x[t] @ dequant(W_gateup[ids[s]]),  slot s = t * top_k + j:
+ *                         the rounding steps of GPTQHIP_OUT_SILU_MUL_PAIRED (accumulators rounded to the activation dtype, SiLU with the accurate
+ *                         expf rounded, product rounded).  x [T, H], act [T * top_k, I], both in the activation dtype.
+ *   gptqhip_moe_down      out[t, :H] = act( sum_j weights[t, j] * (act[t * top_k + j] @ dequant(W_down[ids[t, j]])) ): the per-expert dot products and
+ *                         the weighted sum are fp32, summed in slot order j = 0 .. top_k - 1, and rounded ONCE.  No floating-point atomics: two
+ *                         runs on the same inputs give identical bits.  This is deliberately NOT the HF chain (each expert's output rounded, its
+ *                         product with the routing weight rounded, accumulation in the activation dtype through index_add_): it is the choice
+ *                         the tensor-parallel path made (GPTQHIP_GEMM_PARTIAL_F32: one fp32 sum, one rounding), and it is no further from exact
+ *                         arithmetic than that chain (tests/test_moe_oracle_cpu.py).
+ * Per-weight rounding is the reference's (W = round(scale * (code - zero)), torch.py:716-717), bit-faithful as in decode form 4.
+ * Supported: bits 4; H % 128 == 0, I % 128 == 0; group_size = 128 * 2^n dividing the projection's K (each call takes its own projection's group
+ * size; one group for the whole K included); no act-order permutation; 1 <= T <= 16, 1 <= top_k <= 16; fp16 x fp16, bf16 x bf16 and fp16 activations
+ * x bf16 scales; 16-byte aligned tensors.  Everything else returns GPTQHIP_EINVAL before any device access.
+ * gptqhip_moe_supported: the host-side predicate (no GPU); group_size <= 0 = one group for the whole K of each projection. */
+int gptqhip_moe_supported(int H, int I, int group_size, int bits, int has_perm, int T, int top_k);
+int gptqhip_moe_gate_up(const void* x, const uint32_t* qweight_t, const uint32_t* meta, const int32_t* ids, void* act, int32_t* status,
+                        int T, int top_k, int E, int H, int I, int group_size, int bits, int act_dtype, int scale_dtype,
+                        gptqhip_stream_t stream);
+int gptqhip_moe_down(const void* act, const uint32_t* qweight_t, const uint32_t* meta, const int32_t* ids, const float* weights, void* out,
+                     int32_t* status, int T, int top_k, int E, int H, int I, int group_size, int bits, int act_dtype, int scale_dtype,
+                     gptqhip_stream_t stream);
 
 /* Quantise-and-pack on the device: weight fp32 [N,K] (nn.Linear layout), scales fp32 [G,N], zeros
  * int32 [G,N], g_idx int32 [K] (negative entries wrap by +G) -> checkpoint-layout qweight int32 [K*bits/32, N] and
