@@ -13,11 +13,17 @@ call signature of transformers' experts modules (Qwen3MoeExperts.forward / Mixtr
   Rounding: per-weight rounding and the SiLU chain are the reference's; the top_k expert outputs are combined in ONE fp32 weighted sum in
   slot order and rounded once (include/gptqhip.h), where the HF loop rounds every expert's output and every product and accumulates in the
   activation dtype.
+* grouped path (ops.moe_grouped_supported: the same shapes at ANY T): gptqhip_moe_align + gptqhip_moe_gate_up_grouped + gptqhip_moe_down_grouped
+  + gptqhip_moe_combine -- the slots sorted by expert on the device, every 16-row unit of one expert on the matrix pipe, the same combine
+  contract (one fp32 weighted sum in slot order, one rounding), the same status word, no host synchronisation.  Taken when `grouped_routing`
+  is set and grouped_min_tokens <= T <= grouped_max_tokens (off by default; GPTQHIP_MOE_GROUPED=1 at construction turns it on), and for
+  T > 16 under stream capture, where the host-routed loop cannot run at all.
 * slow path (more tokens, other shapes): the host-routed per-expert loop of the HF module on ops.gemm over views into the same stacked
   buffers -- arithmetically what a loop over the original modules does.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Sequence, Tuple
 
 import torch
@@ -27,6 +33,10 @@ from .. import _lib, ops
 from ..utils.model import deinterleave_gate_up, fuse_gate_up_interleaved
 
 MAX_FAST_TOKENS = 16
+# eager window of the grouped path when grouped_routing is set.  NOT measured yet: the first T the ungrouped ops do not serve,
+# and the ops' slot limit; tests/dev/moe_grouped_probe.py prints the values the measurement rule gives.
+GROUPED_MIN_TOKENS = 17
+GROUPED_MAX_TOKENS = 65536
 
 
 def _interleave_tiled(gate: torch.Tensor, up: torch.Tensor, tiles: int, inner: int, per_lane: int) -> torch.Tensor:
@@ -68,6 +78,12 @@ class HipMoeExperts(nn.Module):
         self.training = False
         self._scratch: Dict[Tuple, Tuple[torch.Tensor, ...]] = {}
         self._fast_ok: Dict[Tuple[int, int], bool] = {}
+        self.grouped_routing = os.environ.get("GPTQHIP_MOE_GROUPED", "0") == "1"
+        self.grouped_min_tokens = GROUPED_MIN_TOKENS
+        self.grouped_max_tokens = GROUPED_MAX_TOKENS
+        self._grouped_ok: Dict[Tuple[int, int], bool] = {}
+        self._grouped_eager: Dict[Tuple, Dict] = {}        # (dtype, device) -> one grow-only buffer set, sliced per call
+        self._grouped_captured: Dict[Tuple, Tuple[torch.Tensor, ...]] = {}      # (T, top_k, dtype, device) -> buffers a graph holds: never freed
 
     def train(self, mode: bool = True):
         if mode:      # the quantised linears it is built from refuse training mode the same way (SUPPORTS_TRAINING = False)
@@ -155,6 +171,74 @@ class HipMoeExperts(nn.Module):
             self._fast_ok[key] = ok
         return ok and dtype in (torch.float16, torch.bfloat16) and not (dtype == torch.bfloat16 and self.scale_dtype == torch.float16)
 
+    def _common_group_size(self) -> int:
+        """The one group_size argument of the shape predicates: -1 = one group for the whole K of each projection, 0 = not servable."""
+        gs = self.gate_up_group_size
+        if gs != self.down_group_size:
+            gs = -1 if (gs == self.hidden_dim and self.down_group_size == self.intermediate_dim) else 0
+        return gs
+
+    def grouped_path(self, T: int, top_k: int, dtype: torch.dtype) -> bool:
+        """Whether the expert-grouped ops can serve this call (the shape predicate; forward() takes them only inside the grouped_routing window
+        or under stream capture)."""
+        key = (T, top_k)
+        ok = self._grouped_ok.get(key)
+        if ok is None:
+            gs = self._common_group_size()
+            ok = gs != 0 and ops.moe_grouped_supported(self.hidden_dim, self.intermediate_dim, gs, self.bits, False, T, top_k, self.num_experts)
+            self._grouped_ok[key] = ok
+        return ok and dtype in (torch.float16, torch.bfloat16) and not (dtype == torch.bfloat16 and self.scale_dtype == torch.float16)
+
+    def _grouped_alloc(self, S: int, T: int, dtype: torch.dtype, device: torch.device) -> Dict:
+        units = ops.moe_grouped_units(S, self.num_experts)
+        i32 = dict(dtype=torch.int32, device=device)
+        return {"S": S, "T": T,
+                "ids": torch.empty(S, **i32), "w": torch.empty(S, dtype=torch.float32, device=device),
+                "sorted": torch.empty(16 * units, **i32), "unit_expert": torch.empty(units, **i32), "num_units": torch.empty(1, **i32),
+                "act": torch.empty(S * self.intermediate_dim, dtype=dtype, device=device),
+                "part": torch.empty(S * self.hidden_dim, dtype=torch.float32, device=device),
+                "out": torch.empty(T * self.hidden_dim, dtype=dtype, device=device)}
+
+    def _grouped_scratch(self, T: int, top_k: int, dtype: torch.dtype, device: torch.device, capturing: bool) -> Dict:
+        S = T * top_k
+        if capturing:       # a graph holds these pointers: one set per signature, never freed or reallocated
+            key = (T, top_k, dtype, device)
+            b = self._grouped_captured.get(key)
+            if b is None:
+                b = self._grouped_captured[key] = self._grouped_alloc(S, T, dtype, device)
+            return b
+        key = (dtype, device)
+        b = self._grouped_eager.get(key)
+        if b is None or b["S"] < S or b["T"] < T:       # grow only: a prefill's varying T shares one set
+            b = self._grouped_eager[key] = self._grouped_alloc(max(S, b["S"] if b else 0), max(T, b["T"] if b else 0), dtype, device)
+        return b
+
+    def _forward_grouped(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor, capturing: bool) -> torch.Tensor:
+        """The four expert-grouped launches.  The result lives in a persistent buffer of this module that the next grouped call overwrites
+        (eager calls share one grow-only buffer set; a captured call owns the set of its (T, top_k, dtype) signature)."""
+        T, top_k = top_k_index.shape
+        S, H, I, E = T * top_k, self.hidden_dim, self.intermediate_dim, self.num_experts
+        b = self._grouped_scratch(T, top_k, hidden_states.dtype, hidden_states.device, capturing)
+        if top_k_index.dtype == torch.int32 and top_k_index.is_contiguous():
+            ids = top_k_index
+        else:
+            ids = b["ids"][:S].view(T, top_k)
+            ids.copy_(top_k_index)
+        if top_k_weights.dtype == torch.float32 and top_k_weights.is_contiguous():
+            w = top_k_weights
+        else:
+            w = b["w"][:S].view(T, top_k)
+            w.copy_(top_k_weights)
+        x = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
+        act, part, out = b["act"][:S * I].view(S, I), b["part"][:S * H].view(S, H), b["out"][:T * H].view(T, H)
+        ops.moe_align(ids, b["sorted"], b["unit_expert"], b["num_units"], self.status, E)
+        ops.moe_gate_up_grouped(x, self.gate_up_qweight, self.gate_up_meta, b["sorted"], b["unit_expert"], b["num_units"], act, top_k, E, I,
+                                self.gate_up_group_size, self.scale_dtype)
+        ops.moe_down_grouped(act, self.down_qweight, self.down_meta, b["sorted"], b["unit_expert"], b["num_units"], part, top_k, E, H,
+                             self.down_group_size, self.scale_dtype)
+        ops.moe_combine(part, ids, w, out, self.status, E)
+        return out
+
     def _scratch_for(self, T: int, top_k: int, dtype: torch.dtype, device: torch.device):
         key = (T, top_k, dtype)
         s = self._scratch.get(key)
@@ -176,6 +260,10 @@ class HipMoeExperts(nn.Module):
         T, top_k = top_k_index.shape
         if T == 0:
             return torch.zeros_like(hidden_states)
+        if self.grouped_routing and self.grouped_min_tokens <= T <= self.grouped_max_tokens and self.grouped_path(T, top_k, hidden_states.dtype):
+            return self._forward_grouped(hidden_states, top_k_index, top_k_weights, torch.cuda.is_current_stream_capturing())
+        if T > MAX_FAST_TOKENS and torch.cuda.is_current_stream_capturing() and self.grouped_path(T, top_k, hidden_states.dtype):
+            return self._forward_grouped(hidden_states, top_k_index, top_k_weights, True)      # the host-routed loop cannot be captured
         if T > MAX_FAST_TOKENS or not self.fast_path(T, top_k, hidden_states.dtype):
             return self._forward_loop(hidden_states, top_k_index, top_k_weights)
         # the result lives in a persistent buffer of this module (one per (T, top_k, dtype)): the next call with that signature overwrites it
@@ -196,8 +284,8 @@ class HipMoeExperts(nn.Module):
         return out
 
     def check_status(self) -> None:
-        """Host read of the device status word (a synchronisation: call it outside the decode loop).  Raises IndexError when a fast-path
-        call since the last check met an expert id outside [0, num_experts) -- that slot contributed zero -- and clears the word."""
+        """Host read of the device status word (a synchronisation: call it outside the decode loop).  Raises IndexError when a fast-path or
+        grouped-path call since the last check met an expert id outside [0, num_experts) -- that slot contributed zero -- and clears the word."""
         if int(self.status.item()) != 0:
             self.status.zero_()
             raise IndexError(f"HipMoeExperts: expert index out of range [0, {self.num_experts}) in a fused MoE call")

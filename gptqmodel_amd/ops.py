@@ -317,6 +317,105 @@ def moe_down(act: torch.Tensor, qweight_t: torch.Tensor, meta: torch.Tensor, ids
     return out
 
 
+def moe_grouped_supported(H: int, I: int, group_size: int, bits: int = 4, has_perm: bool = False, T: int = 1, top_k: int = 1, E: int = 1) -> bool:
+    """True when the expert-grouped MoE ops (moe_align / moe_gate_up_grouped / moe_down_grouped / moe_combine) serve E experts with hidden size H
+    and intermediate size I for T tokens x top_k slots (host logic, no GPU); group_size <= 0: one group for the whole K of each projection."""
+    return bool(_lib.load().gptqhip_moe_grouped_supported(H, I, group_size, bits, 1 if has_perm else 0, T, top_k, E))
+
+
+def moe_grouped_units(S: int, E: int) -> int:
+    """The most 16-row units S slots on E experts can fill (gptqhip_moe_grouped_units): the length of unit_expert, 1 / 16 of sorted_slots."""
+    return int(_lib.load().gptqhip_moe_grouped_units(S, E))
+
+
+def _moe_sort_check(what: str, S: int, E: int, sorted_slots: torch.Tensor, unit_expert: torch.Tensor, num_units: torch.Tensor) -> None:
+    units = moe_grouped_units(S, E)
+    for t, n, name in ((sorted_slots, 16 * units, "sorted_slots"), (unit_expert, units, "unit_expert"), (num_units, 1, "num_units")):
+        if t.dtype != torch.int32 or t.numel() < max(n, 1) or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {name} must be a contiguous int32 tensor with >= {n} elements")
+
+
+def moe_align(ids: torch.Tensor, sorted_slots: torch.Tensor, unit_expert: torch.Tensor, num_units: torch.Tensor, status: torch.Tensor,
+              E: int) -> None:
+    """Stable counting sort of the T * top_k slots by expert id on the device (gptqhip_moe_align): sorted_slots int32 [16 * units] (experts
+    ascending, slots ascending within an expert, -1 padding to 16-row units), unit_expert int32 [units], num_units int32 [1], with
+    units = moe_grouped_units(T * top_k, E); ids outside [0, E) are in no unit and set status to 1."""
+    _require_cuda(ids, sorted_slots, unit_expert, num_units, status)
+    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
+        raise RuntimeError("moe_align: ids must be a contiguous int32 [T, top_k] tensor")
+    if status.dtype != torch.int32 or status.numel() < 1:
+        raise RuntimeError("moe_align: status must be an int32 tensor")
+    T, top_k = ids.shape
+    _moe_sort_check("moe_align", T * top_k, E, sorted_slots, unit_expert, num_units)
+    with torch.cuda.device(ids.device):
+        rc = _lib.load().gptqhip_moe_align(_ptr(ids), _ptr(sorted_slots), _ptr(unit_expert), _ptr(num_units), _ptr(status), T, top_k, E,
+                                           _stream(ids.device))
+    _lib.check(rc, "gptqhip_moe_align")
+
+
+def moe_gate_up_grouped(x: torch.Tensor, qweight_t: torch.Tensor, meta: torch.Tensor, sorted_slots: torch.Tensor, unit_expert: torch.Tensor,
+                        num_units: torch.Tensor, act: torch.Tensor, top_k: int, E: int, I: int, group_size: int, scale_dtype: torch.dtype,
+                        bits: int = 4) -> torch.Tensor:
+    """Stage one on the sorted slots (gptqhip_moe_gate_up_grouped): act[s, :I] of every slot in a unit, the rounding chain of moe_gate_up.
+    x [T, H]; act: >= T * top_k * I elements of x.dtype (rows of slots in no unit are left untouched)."""
+    _require_cuda(x, qweight_t, meta, sorted_slots, unit_expert, num_units, act)
+    if x.dtype not in _DT or scale_dtype not in _DT or x.dim() != 2 or not x.is_contiguous():
+        raise RuntimeError(f"moe_gate_up_grouped: x must be a contiguous 16-bit [T, H] tensor (got {x.dtype} {tuple(x.shape)})")
+    T, H = x.shape
+    _moe_sort_check("moe_gate_up_grouped", T * top_k, E, sorted_slots, unit_expert, num_units)
+    if act.dtype != x.dtype or act.numel() < T * top_k * I or not act.is_contiguous():
+        raise RuntimeError(f"moe_gate_up_grouped: act must be a contiguous {x.dtype} tensor with >= {T * top_k * I} elements")
+    with torch.cuda.device(x.device):
+        rc = _lib.load().gptqhip_moe_gate_up_grouped(_ptr(x), _ptr(qweight_t), _ptr(meta), _ptr(sorted_slots), _ptr(unit_expert), _ptr(num_units),
+                                                     _ptr(act), T, top_k, E, H, I, group_size, bits, _DT[x.dtype], _DT[scale_dtype],
+                                                     _stream(x.device))
+    _lib.check(rc, "gptqhip_moe_gate_up_grouped")
+    return act
+
+
+def moe_down_grouped(act: torch.Tensor, qweight_t: torch.Tensor, meta: torch.Tensor, sorted_slots: torch.Tensor, unit_expert: torch.Tensor,
+                     num_units: torch.Tensor, part: torch.Tensor, top_k: int, E: int, H: int, group_size: int, scale_dtype: torch.dtype,
+                     bits: int = 4) -> torch.Tensor:
+    """Stage two on the sorted slots (gptqhip_moe_down_grouped): part[s, :H] = act[s] @ the down projection of the slot's expert, UNROUNDED
+    fp32.  act [T * top_k, I]; part: >= T * top_k * H float32 elements."""
+    _require_cuda(act, qweight_t, meta, sorted_slots, unit_expert, num_units, part)
+    if act.dtype not in _DT or scale_dtype not in _DT or act.dim() != 2 or not act.is_contiguous() or act.shape[0] % top_k != 0:
+        raise RuntimeError(f"moe_down_grouped: act must be a contiguous 16-bit [T * top_k, I] tensor (got {act.dtype} {tuple(act.shape)})")
+    S, I = act.shape
+    _moe_sort_check("moe_down_grouped", S, E, sorted_slots, unit_expert, num_units)
+    if part.dtype != torch.float32 or part.numel() < S * H or not part.is_contiguous():
+        raise RuntimeError(f"moe_down_grouped: part must be a contiguous float32 tensor with >= {S * H} elements")
+    with torch.cuda.device(act.device):
+        rc = _lib.load().gptqhip_moe_down_grouped(_ptr(act), _ptr(qweight_t), _ptr(meta), _ptr(sorted_slots), _ptr(unit_expert), _ptr(num_units),
+                                                  _ptr(part), S // top_k, top_k, E, H, I, group_size, bits, _DT[act.dtype], _DT[scale_dtype],
+                                                  _stream(act.device))
+    _lib.check(rc, "gptqhip_moe_down_grouped")
+    return part
+
+
+def moe_combine(part: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, out: torch.Tensor, status: torch.Tensor, E: int) -> torch.Tensor:
+    """out[t, :H] = round( sum_j weights[t, j] * part[t * top_k + j] ) (gptqhip_moe_combine): one fp32 sum in slot order, one rounding, ids outside
+    [0, E) skipped -- the contract of moe_down.  part float32 [T * top_k, H], ids int32 / weights float32 [T, top_k], out 16-bit [T, H]."""
+    _require_cuda(part, ids, weights, out, status)
+    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
+        raise RuntimeError("moe_combine: ids must be a contiguous int32 [T, top_k] tensor")
+    T, top_k = ids.shape
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (T, top_k) or not weights.is_contiguous():
+        raise RuntimeError("moe_combine: weights must be a contiguous float32 [T, top_k] tensor")
+    if out.dtype not in _DT or out.dim() != 2 or out.shape[0] != T or not out.is_contiguous():
+        raise RuntimeError("moe_combine: out must be a contiguous 16-bit [T, H] tensor")
+    H = out.shape[1]
+    if part.dtype != torch.float32 or part.numel() < T * top_k * H or not part.is_contiguous():
+        raise RuntimeError(f"moe_combine: part must be a contiguous float32 tensor with >= {T * top_k * H} elements")
+    if status.dtype != torch.int32 or status.numel() < 1:
+        raise RuntimeError("moe_combine: status must be an int32 tensor")
+    with torch.cuda.device(part.device):
+        rc = _lib.load().gptqhip_moe_combine(_ptr(part), _ptr(ids), _ptr(weights), _ptr(out), _ptr(status), T, top_k, E, H, _DT[out.dtype],
+                                             _stream(part.device))
+    _lib.check(rc, "gptqhip_moe_combine")
+    return out
+
+
 def dequant(qweight, qzeros, scales, g_idx, group_size: int, bits: int, out_dtype=None) -> torch.Tensor:
     """[K,N] weights from the CHECKPOINT layout (bit-exact with the reference's dequantize_weight())."""
     lib = _lib.load()

@@ -46,9 +46,10 @@ def _is_moe_block(m) -> bool:
     return bool(mods) and all(_naming(e) is not None for e in mods)
 
 
-def fuse_moe_experts(block: nn.Module) -> bool:
+def fuse_moe_experts(block: nn.Module, grouped_routing: Optional[bool] = None) -> bool:
     """Replace `block.experts` (a container of per-expert HIP GPTQ MLPs) by one HipMoeExperts.  True when replaced; False -- with the reason in
-    `block._gptqhip_moe_skipped` and the block untouched -- otherwise.  Never raises."""
+    `block._gptqhip_moe_skipped` and the block untouched -- otherwise.  Never raises.  grouped_routing: the stand-in's `grouped_routing`
+    attribute (the expert-grouped device-routed path beyond 16 tokens); None keeps its default (GPTQHIP_MOE_GROUPED=1 in the environment)."""
     try:
         from ..nn_modules.moe import HipMoeExperts
         mods = _expert_modules(block)
@@ -72,6 +73,8 @@ def fuse_moe_experts(block: nn.Module) -> bool:
             fused = HipMoeExperts.from_linears(gate, up, down)
         except NotImplementedError as e:
             return _decline(block, f"experts cannot share the stacked layout: {e}")
+        if grouped_routing is not None:
+            fused.grouped_routing = bool(grouped_routing)
         block.experts = fused
         if hasattr(block, "_gptqhip_moe_skipped"):
             del block._gptqhip_moe_skipped
@@ -80,8 +83,8 @@ def fuse_moe_experts(block: nn.Module) -> bool:
         return _decline(block, f"{type(e).__name__}: {e}")
 
 
-def auto_fuse_moe(model: nn.Module) -> int:
-    """fuse_moe_experts on every sparse-MoE block of `model`; returns the number of fused blocks and records
+def auto_fuse_moe(model: nn.Module, grouped_routing: Optional[bool] = None) -> int:
+    """fuse_moe_experts (with `grouped_routing` passed on) on every sparse-MoE block of `model`; returns the number of fused blocks and records
     `model._gptqhip_moe_fused` / `model._gptqhip_moe_skipped` [(block class, reason)].  Models without such blocks see no change.
     Opt-out like auto_fuse: GPTQHIP_AUTO_FUSE=0 in the environment, or `model._gptqhip_auto_fuse = False`."""
     if os.environ.get("GPTQHIP_AUTO_FUSE", "1") == "0" or not isinstance(model, nn.Module) or getattr(model, "_gptqhip_auto_fuse", True) is False:
@@ -92,7 +95,7 @@ def auto_fuse_moe(model: nn.Module) -> int:
             return 0
         fused, skipped = 0, []
         for b in blocks:
-            if fuse_moe_experts(b):
+            if fuse_moe_experts(b, grouped_routing):
                 fused += 1
             else:
                 skipped.append((type(b).__name__, getattr(b, "_gptqhip_moe_skipped", "")))

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define GPTQHIP_ABI_VERSION 20
+#define GPTQHIP_ABI_VERSION 21
 
 /* error codes */
 #define GPTQHIP_OK 0
@@ -253,6 +253,42 @@ int gptqhip_moe_gate_up(const void* x, const uint32_t* qweight_t, const uint32_t
 int gptqhip_moe_down(const void* act, const uint32_t* qweight_t, const uint32_t* meta, const int32_t* ids, const float* weights, void* out,
                      int32_t* status, int T, int top_k, int E, int H, int I, int group_size, int bits, int act_dtype, int scale_dtype,
                      gptqhip_stream_t stream);
+
+/* EXPERT-GROUPED FUSED MoE OPS for any number of tokens (gptqmodel_amd/csrc/gptqhip_moe_grouped.hip): the same stacked weights, routing tensors,
+ * status convention and numerics contract as the two ops above, with the S = T * top_k slots (slot s = t * top_k + j) sorted by expert on the
+ * device, so that every 16-row UNIT of one expert runs through the matrix pipe with all rows carrying real tokens and the expert's weights are
+ * streamed once per unit instead of once per slot.  Four launches whose grids depend only on (T, top_k, E, shapes): nothing synchronises with
+ * the host, the sequence can be captured in a graph at any supported T.
+ *   gptqhip_moe_grouped_units(S, E)  max_units = min(S, (S + 15 * min(S, E)) / 16): the most units S slots on E experts can fill (0 when S < 1 or
+ *                         E < 1).  Sizes the sort buffers and the grids.
+ *   gptqhip_moe_align     a STABLE counting sort of the slots by expert id.  sorted_slots int32 [16 * max_units]: experts in ascending id, expert
+ *                         e's slots in ascending slot index, padded with -1 to a multiple of 16 (an expert without slots takes no unit);
+ *                         unit_expert int32 [max_units]; num_units int32 [1]; both arrays are -1 past num_units.  A slot whose id is outside
+ *                         [0, E) is in no unit and sets `status` to 1.  The buffers are a pure function of ids (no ordering by atomics).
+ *   gptqhip_moe_gate_up_grouped  act[s, :I] for every slot s of a unit, the rounding chain of gptqhip_moe_gate_up.  Rows of act whose slot is in no
+ *                         unit are left untouched.
+ *   gptqhip_moe_down_grouped  part[s, :H] = act[s] @ dequant(W_down[ids[s]]): the UNROUNDED fp32 dot products, float32 [S, H].
+ *   gptqhip_moe_combine   out[t, :H] = act( sum_j weights[t, j] * part[t * top_k + j] ) in fp32, slot order, ONE rounding; a slot whose id is
+ *                         outside [0, E) is skipped whatever its weight (and sets `status`).  No floating-point atomics anywhere; the rows of a
+ *                         unit never mix and the in-block split of K depends on the shape alone, so a token's output bits do not depend on what
+ *                         else is in the batch.  The K summation order differs from gptqhip_moe_gate_up / gptqhip_moe_down: same contract, not
+ *                         the same bits.
+ * Supported: the shape and dtype rules of the ops above (4 bits; H % 128 == 0, I % 128 == 0; group_size = 128 * 2^n dividing the projection's K;
+ * no act-order; the three dtype pairs; 16-byte aligned tensors, 4-byte aligned routing / sort buffers) with T >= 1, 1 <= top_k <= 16,
+ * 1 <= E <= 512 (the align block's LDS: 16 waves x E counters) and S = T * top_k <= 65536.  Everything else returns GPTQHIP_EINVAL before any
+ * device access.  gptqhip_moe_grouped_supported: the host-side predicate (no GPU); group_size <= 0 = one group for the whole K. */
+int gptqhip_moe_grouped_supported(int H, int I, int group_size, int bits, int has_perm, int T, int top_k, int E);
+int gptqhip_moe_grouped_units(int S, int E);
+int gptqhip_moe_align(const int32_t* ids, int32_t* sorted_slots, int32_t* unit_expert, int32_t* num_units, int32_t* status, int T, int top_k,
+                      int E, gptqhip_stream_t stream);
+int gptqhip_moe_gate_up_grouped(const void* x, const uint32_t* qweight_t, const uint32_t* meta, const int32_t* sorted_slots,
+                                const int32_t* unit_expert, const int32_t* num_units, void* act, int T, int top_k, int E, int H, int I,
+                                int group_size, int bits, int act_dtype, int scale_dtype, gptqhip_stream_t stream);
+int gptqhip_moe_down_grouped(const void* act, const uint32_t* qweight_t, const uint32_t* meta, const int32_t* sorted_slots,
+                             const int32_t* unit_expert, const int32_t* num_units, float* part, int T, int top_k, int E, int H, int I,
+                             int group_size, int bits, int act_dtype, int scale_dtype, gptqhip_stream_t stream);
+int gptqhip_moe_combine(const float* part, const int32_t* ids, const float* weights, void* out, int32_t* status, int T, int top_k, int E, int H,
+                        int act_dtype, gptqhip_stream_t stream);
 
 /* Quantise-and-pack on the device: weight fp32 [N,K] (nn.Linear layout), scales fp32 [G,N], zeros
  * int32 [G,N], g_idx int32 [K] (negative entries wrap by +G) -> checkpoint-layout qweight int32 [K*bits/32, N] and
