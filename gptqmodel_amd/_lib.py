@@ -59,6 +59,11 @@ SIGNATURES = {
     "gptqhip_moe_gate_up_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_moe_down_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_moe_combine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "gptqhip_fp8_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "gptqhip_fp8_tiled_bytes": (_sz, [_i, _i]),
+    "gptqhip_fp8_repack": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "gptqhip_fp8_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gptqhip_fp8_dequant": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_pack_gptq": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_pack_gptq_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "gptqhip_gather_cols": (_i, [_vp, _vp, _vp, _i, _i, _vp]),

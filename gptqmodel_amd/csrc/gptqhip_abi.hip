@@ -2,6 +2,8 @@
 // kernel selection.  No torch types and no process-global mutable state: the error string and the tuning
 // overrides (benchmarks / tests) are THREAD-LOCAL, so concurrent callers on different threads, devices or
 // streams never observe each other's settings.
+// The fused MoE entries (gptqhip_moe*.hip) and the FP8 weight-only entries (gptqhip_fp8.hip: gptqhip_fp8_supported / _tiled_bytes / _repack /
+// _gemm / _dequant) validate and launch in their own translation units with set_error / check_hip from here.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>

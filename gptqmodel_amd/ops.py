@@ -416,6 +416,117 @@ def moe_combine(part: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, ou
     return out
 
 
+FP8_SCALE_TENSOR, FP8_SCALE_ROW, FP8_SCALE_BLOCK = 0, 1, 2
+FP8_SCALE_MODES = {"tensor": FP8_SCALE_TENSOR, "row": FP8_SCALE_ROW, "block": FP8_SCALE_BLOCK}
+FP8_FORMATS = {"float8_e4m3fn": 0, "float8_e5m2": 1, "float8_e4m3fnuz": 2, "float8_e8m0fnu": 3}
+FP8_CVT = {"default": 0, "packed": 1, "f32": 2, "bits": 3}
+_DT_OUT = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}
+
+
+def _fp8_block(scale_mode: int, block_size) -> Tuple[int, int]:
+    if scale_mode != FP8_SCALE_BLOCK:
+        return 0, 0
+    if block_size is None or len(block_size) != 2:
+        raise RuntimeError("fp8: block scales need a (rows, cols) block size")
+    return int(block_size[0]), int(block_size[1])
+
+
+def _fp8_scale_count(K: int, N: int, scale_mode: int, br: int, bc: int) -> int:
+    if scale_mode == FP8_SCALE_TENSOR:
+        return 1
+    if scale_mode == FP8_SCALE_ROW:
+        return N
+    return (N // max(br, 1)) * (K // max(bc, 1))
+
+
+def fp8_supported(M: int, K: int, N: int, scale_mode: int, block_size=None, dtype: torch.dtype = torch.float16,
+                  fmt: str = "float8_e4m3fn") -> bool:
+    """True when gptqhip_fp8_gemm serves x [M, K] on an FP8 [N, K] weight with this scale layout (FP8_SCALE_*; block_size = (rows, cols)
+    of the [N, K] weight per scale), activation dtype and float8 format -- gptqhip_fp8_supported, host logic, no GPU."""
+    br, bc = (0, 0) if scale_mode != FP8_SCALE_BLOCK or block_size is None else (int(block_size[0]), int(block_size[1]))
+    return bool(_lib.load().gptqhip_fp8_supported(M, K, N, scale_mode, br, bc, _DT.get(dtype, -1), FP8_FORMATS.get(fmt, -1)))
+
+
+def fp8_repack(weight: torch.Tensor, scale_inv: torch.Tensor, scale_mode: int, block_size=None):
+    """Checkpoint tensors (weight float8_e4m3fn | uint8 [N, K], scale_inv fp32 () | (N,) | (N / br, K / bc)) -> (weight_t uint8 [N * K] in
+    the MFMA-tile-major kernel layout, rscale fp32 = 1 / scale_inv, same shape).  One-time, on the device, in post_init."""
+    lib = _lib.load()
+    _require_cuda(weight, scale_inv)
+    if weight.dim() != 2 or weight.element_size() != 1:
+        raise RuntimeError(f"fp8_repack: weight must be a 2-D one-byte tensor (got {weight.dtype} {tuple(weight.shape)})")
+    N, K = weight.shape
+    br, bc = _fp8_block(scale_mode, block_size)
+    w = weight.contiguous().view(torch.uint8)
+    s = scale_inv.to(torch.float32).contiguous()
+    want = _fp8_scale_count(K, N, scale_mode, br, bc)
+    if s.numel() != want:
+        raise RuntimeError(f"fp8_repack: scale_inv has {s.numel()} elements, the scale layout needs {want}")
+    nbytes = lib.gptqhip_fp8_tiled_bytes(K, N)
+    if nbytes == 0:
+        raise RuntimeError(f"fp8_repack: unsupported shape K={K} N={N} (K % 128 == 0 and N % 16 == 0)")
+    w_t = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    rscale = torch.empty_like(s)
+    with torch.cuda.device(weight.device):
+        rc = lib.gptqhip_fp8_repack(_ptr(w), _ptr(s), _ptr(w_t), _ptr(rscale), K, N, scale_mode, br, bc, _stream(weight.device))
+    _lib.check(rc, "gptqhip_fp8_repack")
+    return w_t, rscale
+
+
+def fp8_gemm(x: torch.Tensor, weight_t: torch.Tensor, rscale: torch.Tensor, bias: Optional[torch.Tensor], N: int, scale_mode: int,
+             block_size=None, out: Optional[torch.Tensor] = None, cvt: str = "default") -> torch.Tensor:
+    """out[M, N] = x[M, K] @ W^T (+ bias) with W = code * rscale, fp32 accumulation and ONE rounding (gptqhip_fp8_gemm): the decode kernel
+    up to 16 rows, the MFMA-tiled general kernel above.  `cvt`: the decode kernel's conversion route (FP8_CVT; a measurement hook)."""
+    lib = _lib.load()
+    if not (x.is_cuda and weight_t.is_cuda and rscale.is_cuda and (bias is None or bias.is_cuda)):
+        raise RuntimeError("gptqmodel_amd HIP ops need tensors on a ROCm device (got a CPU tensor); "
+                           "there is no CPU fallback")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise RuntimeError("fp8_gemm: x must be a contiguous [M,K] tensor")
+    adt = _DT.get(x.dtype)
+    if adt is None:
+        raise RuntimeError(f"fp8_gemm: unsupported activation dtype {x.dtype}")
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N or not bias.is_contiguous()):
+        raise RuntimeError("fp8_gemm: bias must be a contiguous [N] tensor of the activation dtype")
+    M, K = x.shape
+    if weight_t.dtype != torch.uint8 or weight_t.numel() != K * N or rscale.dtype != torch.float32:
+        raise RuntimeError(f"fp8_gemm: weight_t must hold K * N = {K * N} bytes (uint8) and rscale must be float32")
+    br, bc = _fp8_block(scale_mode, block_size)
+    if rscale.numel() != _fp8_scale_count(K, N, scale_mode, br, bc):
+        raise RuntimeError(f"fp8_gemm: rscale has {rscale.numel()} elements, the scale layout needs {_fp8_scale_count(K, N, scale_mode, br, bc)}")
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.numel() != M * N or not out.is_contiguous():
+        raise RuntimeError("fp8_gemm: out must be a contiguous [M,N] tensor of the activation dtype")
+    if M == 0:
+        return out
+    with torch.cuda.device(x.device):
+        rc = lib.gptqhip_fp8_gemm(x.data_ptr(), weight_t.data_ptr(), rscale.data_ptr(), 0 if bias is None else bias.data_ptr(),
+                                  out.data_ptr(), M, K, N, scale_mode, br, bc, adt, FP8_CVT[cvt], _stream_handle(_dev_index(x.device)))
+    if rc != 0:
+        _lib.check(rc, "gptqhip_fp8_gemm")
+    return out
+
+
+def fp8_dequant(weight_t: torch.Tensor, rscale: torch.Tensor, K: int, N: int, scale_mode: int, block_size=None,
+                out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """[K, N] weights from the kernel layout in fp16 | bf16 | fp32, each element rounded once from the fp32 product code * rscale."""
+    lib = _lib.load()
+    _require_cuda(weight_t, rscale)
+    if out_dtype not in _DT_OUT:
+        raise RuntimeError(f"fp8_dequant: unsupported output dtype {out_dtype}")
+    if weight_t.dtype != torch.uint8 or weight_t.numel() != K * N or rscale.dtype != torch.float32:
+        raise RuntimeError(f"fp8_dequant: weight_t must hold K * N = {K * N} bytes (uint8) and rscale must be float32")
+    br, bc = _fp8_block(scale_mode, block_size)
+    if rscale.numel() != _fp8_scale_count(K, N, scale_mode, br, bc):
+        raise RuntimeError(f"fp8_dequant: rscale has {rscale.numel()} elements, the scale layout needs {_fp8_scale_count(K, N, scale_mode, br, bc)}")
+    out = torch.empty((K, N), dtype=out_dtype, device=weight_t.device)
+    with torch.cuda.device(weight_t.device):
+        rc = lib.gptqhip_fp8_dequant(_ptr(weight_t), _ptr(rscale), _ptr(out), K, N, scale_mode, br, bc, _DT_OUT[out_dtype],
+                                     _stream(weight_t.device))
+    _lib.check(rc, "gptqhip_fp8_dequant")
+    return out
+
+
 def dequant(qweight, qzeros, scales, g_idx, group_size: int, bits: int, out_dtype=None) -> torch.Tensor:
     """[K,N] weights from the CHECKPOINT layout (bit-exact with the reference's dequantize_weight())."""
     lib = _lib.load()

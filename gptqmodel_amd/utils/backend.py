@@ -1,7 +1,7 @@
 """BACKEND selector values.  Mirrors gptqmodel/utils/backend.py:10-87 for the members that matter here and
-adds the two members this backend introduces (INTEGRATION.md shows the two-line upstream patch):
+adds the members this backend introduces (INTEGRATION.md shows the two-line upstream patch for the first two):
 
-    GPTQ_HIP = "gptq_hip"     AWQ_HIP = "awq_hip"      (+ method-generic legacy-style alias HIP = "hip")
+    GPTQ_HIP = "gptq_hip"     AWQ_HIP = "awq_hip"     FP8_HIP = "fp8_hip"      (+ method-generic legacy-style alias HIP = "hip")
 """
 from __future__ import annotations
 
@@ -15,6 +15,7 @@ class BACKEND(str, Enum):
     # new: MI355X-native kernels
     GPTQ_HIP = "gptq_hip"
     AWQ_HIP = "awq_hip"
+    FP8_HIP = "fp8_hip"
     HIP = "hip"  # generic alias resolved per quant method, like upstream's TORCH/MARLIN legacy names
     # upstream names kept so that saved configs naming them fail with a clear message instead of a KeyError
     GPTQ_TORCH = "gptq_torch"
@@ -26,6 +27,7 @@ class BACKEND(str, Enum):
 _LEGACY_BACKEND_BY_METHOD = {
     "gptq": {BACKEND.HIP: BACKEND.GPTQ_HIP, BACKEND.TORCH: BACKEND.GPTQ_TORCH},
     "awq": {BACKEND.HIP: BACKEND.AWQ_HIP, BACKEND.TORCH: BACKEND.AWQ_TORCH, BACKEND.TORCH_AWQ: BACKEND.AWQ_TORCH},
+    "fp8": {BACKEND.HIP: BACKEND.FP8_HIP},
 }
 
 

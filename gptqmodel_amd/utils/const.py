@@ -3,7 +3,7 @@ checkpoints' quantize_config.json strings parse identically.
 
 Reference definitions: DEVICE / PLATFORM  gptqmodel/models/_const.py:41-84,
 FORMAT / METHOD  gptqmodel/quantization/config.py:106-141.
-Only the members relevant to the GPTQ/AWQ int4/int8 hot path are listed; the HIP backend is
+Only the members relevant to the GPTQ/AWQ int4/int8 and FP8 weight-only hot paths are listed; the HIP backend is
 `DEVICE.ROCM`-only by construction.
 """
 from __future__ import annotations
@@ -37,11 +37,13 @@ class FORMAT(str, Enum):
     GPTQ_V2 = "gptq_v2"  # qzeros hold zero
     GPTQ_P = "gptq_p"    # planar (split-plane) words, qzeros hold zero: what 5 / 6 / 7-bit checkpoints declare, optional for 3 bits
     GEMM = "gemm"        # AWQ GEMM layout
+    FP8 = "fp8"          # float8 weight-only checkpoints: `weight` fp8 [out, in] + `weight_scale_inv` fp32
 
 
 class METHOD(str, Enum):
     GPTQ = "gptq"
     AWQ = "awq"
+    FP8 = "fp8"
 
 
 IS_ROCM = bool(getattr(torch.version, "hip", None))

@@ -1,8 +1,8 @@
 /*
  * gptqhip.h -- C ABI of libgptqhip.so: the MI355X (gfx950 / CDNA4) GPTQ/AWQ grouped int4/int8
  * dequant-matmul backend.  This is the whole drop-in boundary: plain pointers and sizes, no torch
- * types.  The only callers are the two QuantLinear classes in gptqmodel_amd/nn_modules/qlinear/
- * (HipGptqLinear, HipAwqLinear) through ctypes (gptqmodel_amd/_lib.py); INTEGRATION.md shows the
+ * types.  The only callers are the QuantLinear classes in gptqmodel_amd/nn_modules/qlinear/
+ * (HipGptqLinear, HipAwqLinear, HipFp8Linear) through ctypes (gptqmodel_amd/_lib.py); INTEGRATION.md shows the
  * binding a GPTQModel maintainer would add.
  *
  * Each entry point names the reference interface it replaces (paths relative to the upstream
@@ -47,6 +47,8 @@
 extern "C" {
 #endif
 
+/* Stays 21 with the gptqhip_fp8_* entries: they are purely additive (no existing signature or struct changed), and a library built before
+ * them still fails loudly at load, because the binding resolves every declared symbol by name (gptqmodel_amd/_lib.py: getattr per symbol). */
 #define GPTQHIP_ABI_VERSION 21
 
 /* error codes */
@@ -289,6 +291,53 @@ int gptqhip_moe_down_grouped(const void* act, const uint32_t* qweight_t, const u
                              int group_size, int bits, int act_dtype, int scale_dtype, gptqhip_stream_t stream);
 int gptqhip_moe_combine(const float* part, const int32_t* ids, const float* weights, void* out, int32_t* status, int T, int top_k, int E, int H,
                         int act_dtype, gptqhip_stream_t stream);
+
+/* FP8 WEIGHT-ONLY LINEAR, W8A16 (gptqmodel_amd/csrc/gptqhip_fp8.hip): OCP float8_e4m3fn weights, fp16 | bf16 activations (never quantised), fp32
+ * accumulation.  Replaces TorchFP8Linear (gptqmodel/nn_modules/qlinear/fp8.py:115), METHOD.FP8 / FORMAT.FP8.
+ *   Semantics: W[n, k] = code[n, k] / scale_inv[...] -- the reference's "inverse" scale semantics (fp8.py:350-387) -- with scale_inv fp32 in one of
+ *            three layouts: GPTQHIP_FP8_SCALE_TENSOR [] / _ROW [N] / _BLOCK [N / block_rows, K / block_cols] (fp8.py:198-209).  e4m3 -> fp16 / bf16 is
+ *            exact, so the codes enter the matrix pipe unscaled; 1 / scale_inv (formed ONCE by an IEEE fp32 division, in gptqhip_fp8_repack)
+ *            multiplies the fp32 accumulator -- in the epilogue for tensor / row scales, once per block_cols-wide K block for block scales --
+ *            then the bias is added in fp32 and the sum is rounded ONCE to the activation dtype.  Deliberately NOT the reference's chain
+ *            (fp8.py:423-461: every dequantised weight rounded to the activation dtype, the matmul's rounding, the bias add's rounding): the
+ *            choice of decode form 5 and gptqhip_moe_down, no further from float64 arithmetic than that chain (tests/test_gpu_fp8.py).
+ *   NaN codes (0x7f, 0xff): undefined, never produced by the packer (it clamps to +-448 before the cast, fp8.py:83-92).
+ *   Supported (gptqhip_fp8_supported, host logic, no GPU; everything else returns GPTQHIP_EINVAL before any device access): fp8_format
+ *            GPTQHIP_FP8_E4M3FN only (e5m2 / e4m3fnuz / e8m0fnu are declined); act_dtype fp16 | bf16; K % 128 == 0; N % 16 == 0;
+ *            0 <= M <= 65535 * 64; tensor and row scales; block scales with block_cols % 128 == 0, block_cols | K, block_rows >= 1,
+ *            block_rows | N (a column's scale row is n / block_rows: block_rows need not divide the 16-column tile); 16-byte aligned tensors.
+ *   gptqhip_fp8_tiled_bytes(K, N)  bytes of the kernel layout (= K * N; 0 = unsupported shape).
+ *   gptqhip_fp8_repack    post_init: weight uint8 [N, K] (the checkpoint's `weight`, K contiguous) -> weight_t in the MFMA-tile-major layout
+ *            (2 KiB per (16-column tile, 128-row chunk), gptqhip_fp8.hip) and rscale[i] = 1 / scale_inv[i] (same shape as scale_inv).  Same
+ *            role as gptqhip_repack_tiled; the reference's FP8 class keeps the checkpoint layout (fp8.py:211-232).
+ *   gptqhip_fp8_gemm      out[M, N] = x[M, K] @ W^T (+ bias): replaces TorchFP8Linear.forward (fp8.py:439-461, _forward_dequant_matmul :423).  x / out /
+ *            bias in act_dtype, bias [N] or NULL.  1 <= M <= 16: the HBM-bound decode kernel (one launch, grid a function of (K, N) only, fixed-order
+ *            in-block reduction, no atomics: run-to-run identical bits, and a row's bits do not depend on the other rows of the batch); M >= 17:
+ *            the MFMA-tiled general kernel (no workspace); M == 0: a no-op success.  flags: GPTQHIP_FP8_CVT_* picks the decode kernel's
+ *            e4m3 -> 16-bit conversion route (0 = default; a measurement hook, all routes give the same values).
+ *   gptqhip_fp8_dequant   out[K, N] in out_dtype (fp16 | bf16 | GPTQHIP_FP32) from the kernel layout, each element rounded once from the fp32 product
+ *            code * rscale: serves dequantize_weight() (fp8.py:350-387, which divides in the target dtype instead). */
+#define GPTQHIP_FP32 2                /* out_dtype of gptqhip_fp8_dequant only */
+#define GPTQHIP_FP8_E4M3FN 0
+#define GPTQHIP_FP8_E5M2 1
+#define GPTQHIP_FP8_E4M3FNUZ 2
+#define GPTQHIP_FP8_E8M0FNU 3
+#define GPTQHIP_FP8_SCALE_TENSOR 0
+#define GPTQHIP_FP8_SCALE_ROW 1
+#define GPTQHIP_FP8_SCALE_BLOCK 2
+#define GPTQHIP_FP8_CVT_DEFAULT 0
+#define GPTQHIP_FP8_CVT_PACKED 1      /* v_cvt_scalef32_pk_{f16,bf16}_fp8 (the default)                              */
+#define GPTQHIP_FP8_CVT_F32 2         /* v_cvt_pk_f32_fp8 + a packed fp32 -> 16-bit convert                           */
+#define GPTQHIP_FP8_CVT_BITS 3        /* fp16 only: bit placement = value * 2^-8, the 2^8 applied to the accumulator */
+#define GPTQHIP_FP8_CVT_MASK 3
+int gptqhip_fp8_supported(int M, int K, int N, int scale_mode, int block_rows, int block_cols, int act_dtype, int fp8_format);
+size_t gptqhip_fp8_tiled_bytes(int K, int N);
+int gptqhip_fp8_repack(const uint8_t* weight, const float* scale_inv, uint8_t* weight_t, float* rscale, int K, int N, int scale_mode,
+                       int block_rows, int block_cols, gptqhip_stream_t stream);
+int gptqhip_fp8_gemm(const void* x, const uint8_t* weight_t, const float* rscale, const void* bias, void* out, int M, int K, int N,
+                     int scale_mode, int block_rows, int block_cols, int act_dtype, int flags, gptqhip_stream_t stream);
+int gptqhip_fp8_dequant(const uint8_t* weight_t, const float* rscale, void* out, int K, int N, int scale_mode, int block_rows, int block_cols,
+                        int out_dtype, gptqhip_stream_t stream);
 
 /* Quantise-and-pack on the device: weight fp32 [N,K] (nn.Linear layout), scales fp32 [G,N], zeros
  * int32 [G,N], g_idx int32 [K] (negative entries wrap by +G) -> checkpoint-layout qweight int32 [K*bits/32, N] and
