@@ -41,6 +41,7 @@
 //            pipe takes at face value: tests/dev/mfma_denorm_probe.hip); the 2^8 multiplies the accumulator in the epilogue (exact)
 #include "../../include/gptqhip.h"
 #include "gptqhip_device.h"
+#include "gptqhip_fp8_frag.h"
 #include "gptqhip_host.h"
 
 namespace gptqhip {
@@ -48,13 +49,11 @@ namespace gptqhip {
 constexpr int kFp8DecodeRows = 16;     // rows of the decode kernel (one MFMA tile)
 constexpr int kFp8DecodeWaves = 8;     // most waves of a decode block (in-block split of K)
 constexpr int kFp8Ahead = 4;           // chunks whose loads a decode wave issues before consuming the first
-constexpr int kFp8BlockBytes = 2048;   // one (tile, chunk) block
 constexpr int kFp8GemmWaves = 4;       // general kernel: waves per block
 constexpr int kFp8GemmRT = 4;          //   16-row tiles per block (shared by its waves)
 constexpr int kFp8GemmCT = 2;          //   16-column tiles per wave
 constexpr int kFp8MaxRows = 65535 * 16 * kFp8GemmRT;
 
-constexpr int kCvtPacked = 0, kCvtF32 = 1, kCvtBits = 2;
 constexpr int kScaleTensor = GPTQHIP_FP8_SCALE_TENSOR, kScaleRow = GPTQHIP_FP8_SCALE_ROW, kScaleBlock = GPTQHIP_FP8_SCALE_BLOCK;
 
 struct Fp8Params {
@@ -67,44 +66,6 @@ struct Fp8Params {
     int br, bc;            // block scales: rows (of the [N, K] weight) and columns per scale
     int kbn, cpb;          //               scales per weight row (K / bc), 128-row chunks per scale (bc / 128)
 };
-
-// lane (rq, c)'s 8 consecutive codes of one K-step -> MFMA B fragment (8 x 16-bit, natural k order)
-template <int ACT, int CVT>
-__device__ __forceinline__ u4_t fp8x8_to_frag(uint32_t lo, uint32_t hi) {
-    u4_t r;
-    if constexpr (CVT == kCvtPacked && ACT == kFP16) {
-        r.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false));
-        r.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true));
-        r.z = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false));
-        r.w = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true));
-    } else if constexpr (CVT == kCvtPacked) {
-        r.x = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false));
-        r.y = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true));
-        r.z = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false));
-        r.w = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true));
-    } else if constexpr (CVT == kCvtF32) {
-        auto pair = [](uint32_t w, bool upper) {
-            const auto f = upper ? __builtin_amdgcn_cvt_pk_f32_fp8(w, true) : __builtin_amdgcn_cvt_pk_f32_fp8(w, false);
-            return ACT == kFP16 ? pack_f16(f[0], f[1]) : pack_bf16(f[0], f[1]);   // exact: 4 significant bits
-        };
-        r.x = pair(lo, false);
-        r.y = pair(lo, true);
-        r.z = pair(hi, false);
-        r.w = pair(hi, true);
-    } else {
-        static_assert(ACT == kFP16, "the bit-placement route exists for fp16 only");
-        // bytes (b0, b1) -> the upper bytes of the two halves, then sign stays and exponent | mantissa move down by one: value * 2^-8
-        auto pair = [](uint32_t w, uint32_t sel) {
-            const uint32_t t = __builtin_amdgcn_perm(w, w, sel);
-            return ((t >> 1) & 0x3f803f80u) | (t & 0x80008000u);
-        };
-        r.x = pair(lo, 0x010c000cu);
-        r.y = pair(lo, 0x030c020cu);
-        r.z = pair(hi, 0x010c000cu);
-        r.w = pair(hi, 0x030c020cu);
-    }
-    return r;
-}
 
 template <int ACT>
 __device__ __forceinline__ void store_round(void* out, size_t idx, float v) {

@@ -527,6 +527,75 @@ def fp8_dequant(weight_t: torch.Tensor, rscale: torch.Tensor, K: int, N: int, sc
     return out
 
 
+def moe_fp8_supported(H: int, I: int, gate_up_block_cols: int = 0, down_scale_mode: int = FP8_SCALE_ROW, down_block_size=None, T: int = 1,
+                      top_k: int = 1, dtype: torch.dtype = torch.float16) -> bool:
+    """True when the fused FP8 MoE decode ops (gptqhip_moe_fp8_gate_up / gptqhip_moe_fp8_down) serve experts with hidden size H and intermediate
+    size I for T tokens x top_k slots (host logic, no GPU).  gate_up_block_cols: 0 = one scale per fused column, bc = K-block scales of bc
+    columns; down_scale_mode / down_block_size: the down projection's FP8_SCALE_* layout and (rows, cols) block."""
+    br, bc = (0, 0) if down_scale_mode != FP8_SCALE_BLOCK or down_block_size is None else (int(down_block_size[0]), int(down_block_size[1]))
+    return bool(_lib.load().gptqhip_moe_fp8_supported(H, I, int(gate_up_block_cols), down_scale_mode, br, bc, T, top_k, _DT.get(dtype, -1)))
+
+
+def _moe_fp8_check(what: str, x: torch.Tensor, rows: int, cols: int, ids: torch.Tensor, status: torch.Tensor, weight_t: torch.Tensor,
+                   rscale: torch.Tensor, E: int, w_bytes: int, n_scales: int):
+    if x.dtype not in _DT:
+        raise RuntimeError(f"{what}: unsupported activation dtype {x.dtype}")
+    if x.dim() != 2 or tuple(x.shape) != (rows, cols) or not x.is_contiguous():
+        raise RuntimeError(f"{what}: input must be a contiguous [{rows}, {cols}] tensor (got {tuple(x.shape)})")
+    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
+        raise RuntimeError(f"{what}: ids must be a contiguous int32 [T, top_k] tensor")
+    if status.dtype != torch.int32 or status.numel() < 1:
+        raise RuntimeError(f"{what}: status must be an int32 tensor")
+    if weight_t.dtype != torch.uint8 or weight_t.numel() != E * w_bytes or not weight_t.is_contiguous():
+        raise RuntimeError(f"{what}: weight_t must be a contiguous uint8 tensor of E * {w_bytes} bytes")
+    if rscale.dtype != torch.float32 or rscale.numel() != E * n_scales or not rscale.is_contiguous():
+        raise RuntimeError(f"{what}: rscale must be a contiguous float32 tensor of E * {n_scales} elements")
+
+
+def moe_fp8_gate_up(x: torch.Tensor, weight_t: torch.Tensor, rscale: torch.Tensor, ids: torch.Tensor, act: torch.Tensor, status: torch.Tensor,
+                    E: int, I: int, block_cols: int = 0) -> torch.Tensor:
+    """Stage one of the fused FP8 MoE experts (gptqhip_moe_fp8_gate_up): act[t * top_k + j, :I] = silu(g) * u with g | u = x[t] @ the fused,
+    row-interleaved gate|up weight of expert ids[t, j], read from the stacked kernel-layout bytes [E, 2I * H] and reciprocal scales ([E, 2I], or
+    [E, 2I, H / block_cols] with K-block scales) of all E experts.  x [T, H], ids int32 [T, top_k] (on the device: nothing is read back),
+    act [T * top_k, I] and status (int32, set to 1 by an id outside [0, E)) are the caller's."""
+    _require_cuda(x, weight_t, rscale, ids, act, status)
+    T, top_k = ids.shape if ids.dim() == 2 else (0, 0)
+    H = x.shape[-1]
+    bc = int(block_cols)
+    _moe_fp8_check("moe_fp8_gate_up", x, T, H, ids, status, weight_t, rscale, E, 2 * I * H, 2 * I * (H // bc if bc > 0 else 1))
+    if act.dtype != x.dtype or act.numel() < T * top_k * I or not act.is_contiguous():
+        raise RuntimeError(f"moe_fp8_gate_up: act must be a contiguous {x.dtype} tensor with >= {T * top_k * I} elements")
+    with torch.cuda.device(x.device):
+        rc = _lib.load().gptqhip_moe_fp8_gate_up(_ptr(x), _ptr(weight_t), _ptr(rscale), _ptr(ids), _ptr(act), _ptr(status), T, top_k, E, H, I,
+                                                 bc, _DT[x.dtype], _stream(x.device))
+    _lib.check(rc, "gptqhip_moe_fp8_gate_up")
+    return act
+
+
+def moe_fp8_down(act: torch.Tensor, weight_t: torch.Tensor, rscale: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, out: torch.Tensor,
+                 status: torch.Tensor, E: int, scale_mode: int, block_size=None) -> torch.Tensor:
+    """Stage two (gptqhip_moe_fp8_down): out[t, :H] = round( sum_j weights[t, j] * (act[t * top_k + j] @ down weight of expert ids[t, j]) ), fp32
+    dot products and ONE fp32 weighted sum in slot order, rounded once (deterministic: no atomics).  act [T * top_k, I], weights float32
+    [T, top_k], out [T, H]; weight_t uint8 [E, I * H], rscale float32 [E] | [E, H] | [E, H / br, I / bc]."""
+    _require_cuda(act, weight_t, rscale, ids, weights, out, status)
+    T, top_k = ids.shape if ids.dim() == 2 else (0, 0)
+    I = act.shape[-1]
+    if out.dim() != 2:
+        raise RuntimeError(f"moe_fp8_down: out must be a contiguous {act.dtype} [T, H] tensor")
+    H = out.shape[1]
+    br, bc = _fp8_block(scale_mode, block_size)
+    _moe_fp8_check("moe_fp8_down", act, T * top_k, I, ids, status, weight_t, rscale, E, I * H, _fp8_scale_count(I, H, scale_mode, br, bc))
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (T, top_k) or not weights.is_contiguous():
+        raise RuntimeError("moe_fp8_down: weights must be a contiguous float32 [T, top_k] tensor")
+    if out.dtype != act.dtype or out.shape[0] != T or not out.is_contiguous():
+        raise RuntimeError(f"moe_fp8_down: out must be a contiguous {act.dtype} [T, H] tensor")
+    with torch.cuda.device(act.device):
+        rc = _lib.load().gptqhip_moe_fp8_down(_ptr(act), _ptr(weight_t), _ptr(rscale), _ptr(ids), _ptr(weights), _ptr(out), _ptr(status), T, top_k,
+                                              E, H, I, scale_mode, br, bc, _DT[act.dtype], _stream(act.device))
+    _lib.check(rc, "gptqhip_moe_fp8_down")
+    return out
+
+
 def dequant(qweight, qzeros, scales, g_idx, group_size: int, bits: int, out_dtype=None) -> torch.Tensor:
     """[K,N] weights from the CHECKPOINT layout (bit-exact with the reference's dequantize_weight())."""
     lib = _lib.load()

@@ -1,12 +1,13 @@
-"""Sparse mixture-of-experts blocks onto the fused MoE decode ops (nn_modules/moe.py: HipMoeExperts).
+"""Sparse mixture-of-experts blocks onto the fused MoE decode ops (nn_modules/moe.py: HipMoeExperts; nn_modules/moe_fp8.py: HipFp8MoeExperts).
 
 `fuse_moe_experts(block)` recognises a sparse-MoE block whose `experts` is a container of per-expert MLP modules -- `gate_proj` / `up_proj` /
 `down_proj`, or Mixtral's `w1` / `w3` / `w2` -- all of them adapter-free 4-bit HIP GPTQ linears of equal shapes, group size and dtype without
-act-order, and replaces `block.experts` by one HipMoeExperts.  The stand-in serves the call the block's forward makes under the installed
-transformers release, `self.experts(hidden_states, top_k_index, top_k_weights)`; a bare nn.ModuleList has no such call (the block's own
-forward indexes it) and is left alone.  Anything not recognised is left untouched with the reason recorded on the block
-(`block._gptqhip_moe_skipped`); the helper never raises.  `auto_fuse_moe(model)` applies it to every such block (the tail of
-utils.hf_llama.auto_fuse, so both post-init routes get it; GPTQHIP_AUTO_FUSE=0 opts out)."""
+act-order, and replaces `block.experts` by one HipMoeExperts.  A block whose projections are ALL HipFp8Linear (float8_e4m3fn, one scale layout
+for gate / up and one for down) gets one HipFp8MoeExperts the same way; a mix of FP8 and other projections is declined.  The stand-in serves
+the call the block's forward makes under the installed transformers release, `self.experts(hidden_states, top_k_index, top_k_weights)`; a bare
+nn.ModuleList has no such call (the block's own forward indexes it) and is left alone.  Anything not recognised is left untouched with the
+reason recorded on the block (`block._gptqhip_moe_skipped`); the helper never raises.  `auto_fuse_moe(model)` applies it to every such block
+(the tail of utils.hf_llama.auto_fuse, so both post-init routes get it; GPTQHIP_AUTO_FUSE=0 opts out)."""
 from __future__ import annotations
 
 import os
@@ -47,16 +48,18 @@ def _is_moe_block(m) -> bool:
 
 
 def fuse_moe_experts(block: nn.Module, grouped_routing: Optional[bool] = None) -> bool:
-    """Replace `block.experts` (a container of per-expert HIP GPTQ MLPs) by one HipMoeExperts.  True when replaced; False -- with the reason in
-    `block._gptqhip_moe_skipped` and the block untouched -- otherwise.  Never raises.  grouped_routing: the stand-in's `grouped_routing`
-    attribute (the expert-grouped device-routed path beyond 16 tokens); None keeps its default (GPTQHIP_MOE_GROUPED=1 in the environment)."""
+    """Replace `block.experts` (a container of per-expert HIP GPTQ MLPs) by one HipMoeExperts, or (of per-expert HIP FP8 MLPs) by one
+    HipFp8MoeExperts.  True when replaced; False -- with the reason in `block._gptqhip_moe_skipped` and the block untouched -- otherwise.
+    Never raises.  grouped_routing: the HipMoeExperts stand-in's `grouped_routing` attribute (the expert-grouped device-routed path beyond 16
+    tokens, which the FP8 stand-in does not have); None keeps its default (GPTQHIP_MOE_GROUPED=1 in the environment)."""
     try:
         from ..nn_modules.moe import HipMoeExperts
+        from ..nn_modules.moe_fp8 import HipFp8MoeExperts
         mods = _expert_modules(block)
         if not mods:
             return _decline(block, "no container of per-expert modules under `experts`")
         experts = block.experts
-        if isinstance(experts, HipMoeExperts):
+        if isinstance(experts, (HipMoeExperts, HipFp8MoeExperts)):
             return _decline(block, "already fused")
         if type(experts).forward is nn.Module.forward:
             return _decline(block, f"{type(experts).__name__} is indexed by the block's own forward: there is no "
@@ -69,11 +72,15 @@ def fuse_moe_experts(block: nn.Module, grouped_routing: Optional[bool] = None) -
             if act is not None and not (isinstance(act, nn.SiLU) or type(act).__name__ in ("SiLU", "SiLUActivation")):
                 return _decline(block, "expert activation is not SiLU")
         gate, up, down = ([getattr(e, n) for e in mods] for n in names)
+        kinds = {getattr(m, "QUANT_TYPE", "") for m in gate + up + down}
+        if "hip_fp8" in kinds and len(kinds) > 1:
+            return _decline(block, f"experts mix FP8 and other projections ({', '.join(sorted(str(k) or 'unquantised' for k in kinds))})")
+        fused_cls = HipFp8MoeExperts if kinds == {"hip_fp8"} else HipMoeExperts
         try:
-            fused = HipMoeExperts.from_linears(gate, up, down)
+            fused = fused_cls.from_linears(gate, up, down)
         except NotImplementedError as e:
             return _decline(block, f"experts cannot share the stacked layout: {e}")
-        if grouped_routing is not None:
+        if grouped_routing is not None and fused_cls is HipMoeExperts:
             fused.grouped_routing = bool(grouped_routing)
         block.experts = fused
         if hasattr(block, "_gptqhip_moe_skipped"):

@@ -47,8 +47,9 @@
 extern "C" {
 #endif
 
-/* Stays 21 with the gptqhip_fp8_* entries: they are purely additive (no existing signature or struct changed), and a library built before
- * them still fails loudly at load, because the binding resolves every declared symbol by name (gptqmodel_amd/_lib.py: getattr per symbol). */
+/* Stays 21 with the gptqhip_fp8_* and gptqhip_moe_fp8_* entries: they are purely additive (no existing signature or struct changed), and a
+ * library built before them still fails loudly at load, because the binding resolves every declared symbol by name (gptqmodel_amd/_lib.py:
+ * getattr per symbol). */
 #define GPTQHIP_ABI_VERSION 21
 
 /* error codes */
@@ -338,6 +339,32 @@ int gptqhip_fp8_gemm(const void* x, const uint8_t* weight_t, const float* rscale
                      int scale_mode, int block_rows, int block_cols, int act_dtype, int flags, gptqhip_stream_t stream);
 int gptqhip_fp8_dequant(const uint8_t* weight_t, const float* rscale, void* out, int K, int N, int scale_mode, int block_rows, int block_cols,
                         int out_dtype, gptqhip_stream_t stream);
+
+/* FUSED FP8 MIXTURE-OF-EXPERTS DECODE OPS for a few tokens (gptqmodel_amd/csrc/gptqhip_moe_fp8.hip): gptqhip_moe_gate_up / gptqhip_moe_down on
+ * float8_e4m3fn experts.  Same routing tensors (ids int32 [T, top_k], weights float32 [T, top_k], on the device), grids that depend on
+ * (T, top_k, shapes) only, no floating-point atomics, capturable; 1 <= T, top_k <= 16.  Every expert's weights are in the layout of
+ * gptqhip_fp8_repack and STACKED at a constant stride:
+ *   gate|up  weight_t uint8 [E, 2I * H]: per expert the [2I, H] weight whose rows interleave gate and up in blocks of 8 (fused rows 16 t .. 16 t + 7
+ *            = gate rows 8 t .. 8 t + 7, fused rows 16 t + 8 .. 16 t + 15 = up rows 8 t .. 8 t + 7), so a 16-column tile holds both halves of 8 MLP
+ *            neurons.  rscale float32, ONE SCALE ROW PER FUSED COLUMN: block_cols = 0: [E, 2I]; block_cols = bc: [E, 2I, H / bc] (what
+ *            gptqhip_fp8_gemm takes as block (1, bc) on expert e's view).
+ *   down     weight_t uint8 [E, I * H], rscale float32 [E] (GPTQHIP_FP8_SCALE_TENSOR) | [E, H] (_ROW) | [E, H / block_rows, I / block_cols] (_BLOCK).
+ *   gptqhip_moe_fp8_gate_up  act[s, :I] = act(act(silu(y_g)) * y_u), y = act(sum_kb rscale * (x[t] . codes)) for the gate and the up column of each
+ *            neuron, slot s = t * top_k + j on expert ids[s]: the rounding chain of gptqhip_moe_gate_up (silu with the accurate expf) on the
+ *            arithmetic of gptqhip_fp8_gemm (exact codes on the matrix pipe, fp32 sums, the reciprocal scale on the accumulator).
+ *   gptqhip_moe_fp8_down     out[t, :H] = act( sum_j weights[t, j] * (act[t * top_k + j] . W_down[ids[t, j]]) ): fp32 dot products, ONE fp32 weighted
+ *            sum in slot order, ONE rounding -- the contract of gptqhip_moe_down.
+ * An expert id outside [0, E) dereferences nothing, contributes zero (gate_up writes zeros for the slot) and sets *status to 1.  NaN codes are
+ * undefined, as in gptqhip_fp8_gemm.  Supported (gptqhip_moe_fp8_supported, host logic, no GPU; everything else returns GPTQHIP_EINVAL with a
+ * message before any device access): H % 128 == 0, I % 128 == 0, act_dtype fp16 | bf16, block columns a multiple of 128 dividing the projection's
+ * K, block rows dividing H.  x / act / weight_t / out must be 16-byte aligned; rscale / ids / weights / status 4-byte aligned. */
+int gptqhip_moe_fp8_supported(int H, int I, int gate_up_block_cols, int down_scale_mode, int down_block_rows, int down_block_cols, int T, int top_k,
+                              int act_dtype);
+int gptqhip_moe_fp8_gate_up(const void* x, const uint8_t* weight_t, const float* rscale, const int32_t* ids, void* act, int32_t* status, int T,
+                            int top_k, int E, int H, int I, int block_cols, int act_dtype, gptqhip_stream_t stream);
+int gptqhip_moe_fp8_down(const void* act, const uint8_t* weight_t, const float* rscale, const int32_t* ids, const float* weights, void* out,
+                         int32_t* status, int T, int top_k, int E, int H, int I, int scale_mode, int block_rows, int block_cols, int act_dtype,
+                         gptqhip_stream_t stream);
 
 /* Quantise-and-pack on the device: weight fp32 [N,K] (nn.Linear layout), scales fp32 [G,N], zeros
  * int32 [G,N], g_idx int32 [K] (negative entries wrap by +G) -> checkpoint-layout qweight int32 [K*bits/32, N] and
