@@ -7,38 +7,24 @@
 //
 //   moe_gate_up_kernel   grid (2I / 16 column tiles, T * top_k slots); slot s = t * top_k + j reads x[t] and expert ids[s].  The fused gate|up
 //                        projection's columns are interleaved in blocks of 8 (utils.model.fuse_gate_up_interleaved), so a 16-column tile holds both
-//                        halves of 8 MLP neurons and the epilogue writes act[s, 8 tile .. 8 tile + 8) directly, with the rounding chain of
-//                        GPTQHIP_OUT_SILU_MUL_PAIRED: y = act(acc), a = act(act(silu(y)) * up), silu with the accurate expf.
+//                        halves of 8 MLP neurons and the epilogue writes act[s, 8 tile .. 8 tile + 8) directly, with the SiLU * up rounding chain
+//                        (gptqhip_moe_common.h: moe_silu_up).
 //   moe_down_kernel      grid (H / 16 column tiles, T tokens); the block's waves are dealt to the token's top_k slots (wps waves per slot, each taking
-//                        every wps-th 128-row chunk of its slot's expert), park their fp32 partial sums in LDS, and wave 0 forms
-//                            out[t, n] = act( sum_{j = 0 .. top_k - 1} weights[t, j] * ( sum_{s = 0 .. wps - 1} partial[j, s][n] ) )
-//                        in that fixed order: fp32 dot products, ONE fp32 weighted sum in slot order, ONE rounding.  No floating-point atomics:
-//                        two runs on the same inputs give the same bits.  This is deliberately NOT the chain of the HF experts loop (which rounds
-//                        every expert's output, rounds its product with the routing weight, and accumulates in the activation dtype through
-//                        index_add_); it is the choice the tensor-parallel path made (one fp32 sum, one rounding).
+//                        every wps-th 128-row chunk of its slot's expert), park their fp32 partial sums in LDS, and wave 0 combines them: ONE fp32
+//                        weighted sum in slot order, ONE rounding (the combine contract, gptqhip_moe_common.h: moe_combine_slots).
 //
 // Both kernels contract on the matrix pipe like the decode kernel at one row, with per-weight rounding kept (dequant_word4: the reference's
 // W = round(scale * (code - zero)), bit-faithful as in decode form 4).  A wave's work item is one (16-column tile, 128-row chunk) block:
 //   * ONE non-temporal 16 B-per-lane load = the block's 1 KiB of codes, one 4 B-per-lane load of the group constants (group_size = 128 * 2^n:
 //     one constant per chunk and column), and ONE 16 B-per-lane load of the chunk's 128 activations: lane (rq, c) takes the 8 values of K-step
-//     (c & 3), rows 8 rq .. 8 rq + 7, so MFMA row m carries the activations of K-step m & 3.  K-step j then runs with the A rows of the other
-//     K-steps masked to zero: accumulator row m ends up with the partial dot product of K-step m & 3 alone, and rows 0 .. 3 (the four
-//     accumulator registers of lanes 0 .. 15) add up to the chunk's dot product.  One activation load per chunk instead of four broadcast ones.
+//     (c & 3), rows 8 rq .. 8 rq + 7 (the masked K-steps of gptqhip_moe_common.h).
 //   * up to four chunks' loads are issued before the first is consumed (16 + 16 + 4 VGPRs per chunk in flight).
 // LDS: 16 x 16 floats of reduction rows (1 KiB); VGPRs stay under 128, so the 1024-thread down blocks launch and 2048 threads fit a CU.
 //
-// Expert ids outside [0, E) dereference nothing: the slot contributes zero (gate_up writes zeros for it) and the device status word is set to 1
-// (the convention of gptqhip_embedding).
-#include "../../include/gptqhip.h"
-#include "gptqhip_device.h"
-#include "gptqhip_host.h"
+// Expert ids outside [0, E) dereference nothing: the slot contributes zero (gate_up writes zeros for it) and the device status word is set to 1.
+#include "gptqhip_moe_common.h"
 
 namespace gptqhip {
-
-constexpr int kMoeMaxRows = 16;      // tokens per call, and slots per token
-constexpr int kMoeGateUpWaves = 8;   // most waves of a gate_up block (in-block split-K)
-constexpr int kMoeDownWaves = 16;    // most waves of a down block
-constexpr int kMoeAhead = 4;         // chunks whose loads a wave issues before consuming the first
 
 struct MoeParams {
     const uint16_t* x;       // gate_up: [T, H]; down: act [T * top_k, I]
@@ -61,8 +47,7 @@ __device__ __forceinline__ float wave_partial(const uint32_t* __restrict__ wt, c
     const DequantConsts kc = make_dequant_consts<4>();
     const int c16 = lane & 15, rq = lane >> 4;
     uint32_t mask[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) mask[j] = (c16 & 3) == j ? 0xffffffffu : 0u;
+    moe_kstep_masks(c16, mask);
     const uint16_t* xl = xrow + 32 * (c16 & 3) + 8 * rq;
     f4_t acc = {0.f, 0.f, 0.f, 0.f};
     for (int base = ck0; base < chunks; base += step * kMoeAhead) {
@@ -80,19 +65,11 @@ __device__ __forceinline__ float wave_partial(const uint32_t* __restrict__ wt, c
             if (base + u * step < chunks) {   // wave-uniform
                 const ColConst cc = expand_meta<4, SCL>(m[u]);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    u4_t aj;
-                    aj.x = a[u].x & mask[j];
-                    aj.y = a[u].y & mask[j];
-                    aj.z = a[u].z & mask[j];
-                    aj.w = a[u].w & mask[j];
-                    acc = mfma16<ACT>(aj, dequant_word4<ACT, SCL>(w[u][j], cc, kc), acc);
-                }
+                for (int j = 0; j < 4; ++j) acc = mfma16<ACT>(moe_masked_a(a[u], mask[j]), dequant_word4<ACT, SCL>(w[u][j], cc, kc), acc);
             }
         }
     }
-    // accumulator register i of lanes 0 .. 15 = row i = K-step i's share
-    return rq == 0 ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : 0.f;
+    return moe_lane_sum(acc, rq);
 }
 
 template <int ACT, int SCL>
@@ -102,11 +79,8 @@ __global__ __launch_bounds__(64 * kMoeGateUpWaves) void moe_gate_up_kernel(MoePa
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
     const int inter = p.N >> 1;
     const int e = p.ids[slot];
-    if (e < 0 || e >= p.E) {   // block-uniform
-        if (threadIdx.x < 8) p.out[(size_t)slot * inter + tile * 8 + threadIdx.x] = 0;
-        if (threadIdx.x == 0) *p.status = 1;
-        return;
-    }
+    uint16_t* out8 = p.out + (size_t)slot * inter + tile * 8;
+    if (moe_gate_up_invalid(e, p.E, out8, p.status)) return;
     const uint32_t* wt = p.qw + (size_t)e * p.w_stride + (size_t)tile * p.chunks * 256;
     const uint32_t* mt = p.meta + (size_t)e * p.m_stride + (size_t)tile * p.G * 16;
     const uint16_t* xrow = p.x + (size_t)(slot / p.top_k) * p.K;
@@ -116,11 +90,8 @@ __global__ __launch_bounds__(64 * kMoeGateUpWaves) void moe_gate_up_kernel(MoePa
     if (wave != 0) return;
     float v = 0.f;
     for (int w = 0; w < W; ++w) v += red[w][lane & 15];
-    // lanes 0 .. 7 hold gate columns, lanes 8 .. 15 the matching up columns: HF's act_fn(gate) * up, every step rounded in the activation dtype
-    const float y = round_through<ACT>(v);
-    const float up = __shfl_down(y, 8);
-    const float a = round_through<ACT>(y / (1.0f + expf(-y))) * up;   // expf, not __expf: HF evaluates SiLU with the accurate exp
-    if (lane < 8) p.out[(size_t)slot * inter + tile * 8 + lane] = f32_to_16<ACT>(a);
+    const uint16_t a = moe_silu_up<ACT>(v);   // lanes 0 .. 7 hold gate columns, lanes 8 .. 15 the matching up columns
+    if (lane < 8) out8[lane] = a;
 }
 
 template <int ACT, int SCL>
@@ -141,88 +112,18 @@ __global__ __launch_bounds__(64 * kMoeDownWaves) void moe_down_kernel(MoeParams 
     }
     if (lane < 16) red[wave][lane] = part;
     __syncthreads();
-    if (wave != 0 || lane >= 16) return;
-    float y = 0.f;
-    for (int jj = 0; jj < p.top_k; ++jj) {   // slot order; an out-of-range expert contributes nothing, whatever its routing weight
-        const int ej = p.ids[t * p.top_k + jj];
-        if (ej < 0 || ej >= p.E) continue;
-        float d = 0.f;
-        for (int s = 0; s < p.wps; ++s) d += red[jj * p.wps + s][lane];
-        y += p.weights[t * p.top_k + jj] * d;
-    }
-    p.out[(size_t)t * p.N + tile * 16 + lane] = f32_to_16<ACT>(y);
-}
-
-static bool moe_group_ok(int K, int group_size) {   // 128 * 2^n dividing K (one group for the whole K included)
-    if (group_size < 128 || K % group_size != 0) return false;
-    const int q = group_size / 128;
-    return group_size % 128 == 0 && (q & (q - 1)) == 0;
-}
-
-static bool moe_shape_ok(int H, int I, int gs_gate_up, int gs_down, int bits, int T, int top_k) {
-    return bits == 4 && H > 0 && I > 0 && H % 128 == 0 && I % 128 == 0 && moe_group_ok(H, gs_gate_up) && moe_group_ok(I, gs_down) &&
-           T >= 1 && T <= kMoeMaxRows && top_k >= 1 && top_k <= kMoeMaxRows;
+    moe_combine_slots<ACT>(red, wave, lane, p.ids + t * p.top_k, p.weights + t * p.top_k, p.top_k, p.E, p.wps, p.out + (size_t)t * p.N + tile * 16,
+                           [](float d, int) { return d; });
 }
 
 static int moe_validate(const char* fn, const void* const* ptrs16, int n16, const void* const* ptrs4, int n4, int T, int top_k, int E, int H, int I,
                         int K, int group_size, int bits, int act_dtype, int scale_dtype) {
-    for (int i = 0; i < n16 + n4; ++i) {
-        if ((i < n16 ? ptrs16[i] : ptrs4[i - n16]) == nullptr) {
-            set_error("%s: null tensor pointer", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    for (int i = 0; i < n16; ++i) {
-        if (reinterpret_cast<uintptr_t>(ptrs16[i]) % 16 != 0) {
-            set_error("%s: activations, weights, constants and outputs must be 16-byte aligned", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    for (int i = 0; i < n4; ++i) {
-        if (reinterpret_cast<uintptr_t>(ptrs4[i]) % 4 != 0) {
-            set_error("%s: ids, weights and status must be 4-byte aligned", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    if (T < 1 || T > kMoeMaxRows || top_k < 1 || top_k > kMoeMaxRows) {
-        set_error("%s: T=%d and top_k=%d must be 1..%d", fn, T, top_k, kMoeMaxRows);
-        return GPTQHIP_EINVAL;
-    }
-    if (E < 1) {
-        set_error("%s: E=%d experts", fn, E);
-        return GPTQHIP_EINVAL;
-    }
-    if (bits != 4 || H <= 0 || I <= 0 || H % 128 != 0 || I % 128 != 0 || !moe_group_ok(K, group_size)) {
-        set_error("%s: unsupported shape H=%d I=%d group_size=%d bits=%d (4 bits, H and I multiples of 128, group_size = 128 * 2^n dividing K=%d)",
-                  fn, H, I, group_size, bits, K);
-        return GPTQHIP_EINVAL;
-    }
-    if ((act_dtype != GPTQHIP_FP16 && act_dtype != GPTQHIP_BF16) || (scale_dtype != GPTQHIP_FP16 && scale_dtype != GPTQHIP_BF16) ||
-        (act_dtype == GPTQHIP_BF16 && scale_dtype == GPTQHIP_FP16)) {
-        set_error("%s: unsupported dtypes act=%d scales=%d (fp16 x fp16, bf16 x bf16, fp16 activations x bf16 scales)", fn, act_dtype, scale_dtype);
-        return GPTQHIP_EINVAL;
-    }
-    return GPTQHIP_OK;
+    int rc = moe_check_ptrs(fn, ptrs16, n16, "activations, weights, constants and outputs", ptrs4, n4, "ids, weights and status");
+    if (!rc) rc = moe_check_few_tokens(fn, T, top_k, E);
+    if (!rc) rc = moe_check_int4_shape(fn, H, I, K, group_size, bits);
+    if (!rc) rc = moe_check_dtypes(fn, act_dtype, scale_dtype);
+    return rc;
 }
-
-template <template <int, int> class Launch>
-static void moe_dispatch(int act_dtype, int scale_dtype, const MoeParams& p, dim3 grid, dim3 block, hipStream_t stream) {
-    if (act_dtype == GPTQHIP_FP16 && scale_dtype == GPTQHIP_FP16) Launch<kFP16, kFP16>::go(p, grid, block, stream);
-    else if (act_dtype == GPTQHIP_BF16) Launch<kBF16, kBF16>::go(p, grid, block, stream);
-    else Launch<kFP16, kBF16>::go(p, grid, block, stream);
-}
-template <int ACT, int SCL>
-struct LaunchGateUp {
-    static void go(const MoeParams& p, dim3 grid, dim3 block, hipStream_t stream) {
-        hipLaunchKernelGGL((moe_gate_up_kernel<ACT, SCL>), grid, block, 0, stream, p);
-    }
-};
-template <int ACT, int SCL>
-struct LaunchDown {
-    static void go(const MoeParams& p, dim3 grid, dim3 block, hipStream_t stream) {
-        hipLaunchKernelGGL((moe_down_kernel<ACT, SCL>), grid, block, 0, stream, p);
-    }
-};
 
 static MoeParams moe_params(const void* x, const uint32_t* qw, const uint32_t* meta, const int32_t* ids, const float* weights, void* out,
                             int32_t* status, int top_k, int E, int K, int N, int group_size) {
@@ -256,7 +157,10 @@ extern "C" {
 int gptqhip_moe_supported(int H, int I, int group_size, int bits, int has_perm, int T, int top_k) {
     if (has_perm) return 0;
     // group_size <= 0: one group for the whole K of each projection (group_size = -1 checkpoints)
-    return moe_shape_ok(H, I, group_size <= 0 ? H : group_size, group_size <= 0 ? I : group_size, bits, T, top_k) ? 1 : 0;
+    return moe_int4_shape_ok(H, I, H, group_size <= 0 ? H : group_size, bits) && moe_int4_shape_ok(H, I, I, group_size <= 0 ? I : group_size, bits) &&
+                   moe_few_tokens_ok(T, top_k)
+               ? 1
+               : 0;
 }
 
 int gptqhip_moe_gate_up(const void* x, const uint32_t* qweight_t, const uint32_t* meta, const int32_t* ids, void* act, int32_t* status,
@@ -268,7 +172,10 @@ int gptqhip_moe_gate_up(const void* x, const uint32_t* qweight_t, const uint32_t
     if (rc) return rc;
     const MoeParams p = moe_params(x, qweight_t, meta, ids, nullptr, act, status, top_k, E, H, 2 * I, group_size);
     const int waves = p.chunks < kMoeGateUpWaves ? p.chunks : kMoeGateUpWaves;
-    moe_dispatch<LaunchGateUp>(act_dtype, scale_dtype, p, dim3(2 * I / kTileN, T * top_k), dim3(64 * waves), reinterpret_cast<hipStream_t>(stream));
+    const dim3 grid(2 * I / kTileN, T * top_k), block(64 * waves);
+    moe_dispatch(act_dtype, scale_dtype, [&](auto a, auto s) {
+        hipLaunchKernelGGL((moe_gate_up_kernel<decltype(a)::value, decltype(s)::value>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), p);
+    });
     return check_hip(hipGetLastError(), "moe_gate_up_kernel launch");
 }
 
@@ -282,7 +189,10 @@ int gptqhip_moe_down(const void* act, const uint32_t* qweight_t, const uint32_t*
     MoeParams p = moe_params(act, qweight_t, meta, ids, weights, out, status, top_k, E, I, H, group_size);
     const int per_slot = kMoeDownWaves / top_k;
     p.wps = p.chunks < per_slot ? p.chunks : per_slot;
-    moe_dispatch<LaunchDown>(act_dtype, scale_dtype, p, dim3(H / kTileN, T), dim3(64 * p.wps * top_k), reinterpret_cast<hipStream_t>(stream));
+    const dim3 grid(H / kTileN, T), block(64 * p.wps * top_k);
+    moe_dispatch(act_dtype, scale_dtype, [&](auto a, auto s) {
+        hipLaunchKernelGGL((moe_down_kernel<decltype(a)::value, decltype(s)::value>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), p);
+    });
     return check_hip(hipGetLastError(), "moe_down_kernel launch");
 }
 

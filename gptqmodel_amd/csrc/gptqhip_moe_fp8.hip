@@ -7,18 +7,15 @@
 //
 //   moe_fp8_gate_up_kernel  grid (2I / 16 column tiles, T * top_k slots), min(8, chunks) waves; slot s = t * top_k + j reads x[t] and expert ids[s].
 //                           The fused gate|up weight interleaves gate and up rows in blocks of 8, so a 16-column tile holds both halves of 8 MLP
-//                           neurons.  Fixed-order LDS reduction over the waves, then the rounding chain of GPTQHIP_OUT_SILU_MUL_PAIRED, as in
-//                           moe_gate_up_kernel: y = act(v) for gate and up, act(silu(y)) with the accurate expf, the product rounded.
+//                           neurons.  Fixed-order LDS reduction over the waves, then the SiLU * up rounding chain (gptqhip_moe_common.h: moe_silu_up).
 //   moe_fp8_down_kernel     grid (H / 16 column tiles, T tokens); the block's waves are dealt to the token's top_k slots (wps = min(16 / top_k,
-//                           chunks) waves per slot), park their fp32 partial sums in LDS, and wave 0 forms
-//                               out[t, n] = act( sum_{j = 0 .. top_k - 1} weights[t, j] * ( sum_{s = 0 .. wps - 1} partial[j, s][n] ) )
-//                           in that fixed order: ONE fp32 weighted sum in slot order, ONE rounding -- the contract of moe_down_kernel.
+//                           chunks) waves per slot), park their fp32 partial sums in LDS, and wave 0 combines them: ONE fp32 weighted sum in slot
+//                           order, ONE rounding (the combine contract, gptqhip_moe_common.h: moe_combine_slots).
 //
 // A wave's work item is one 2 KiB block: two non-temporal 16 B-per-lane loads, the codes converted EXACTLY to fp16 / bf16 (fp8x8_to_frag, the packed
-// convert), and ONE 16 B-per-lane load of the chunk's 128 activations with the masked-K-step scheme of gptqhip_moe.hip (lane (rq, c) takes the 8
-// values of K-step c & 3, K-step j runs with the A rows of the other K-steps masked to zero, accumulator rows 0 .. 3 add up to the chunk's dot
-// product).  Up to four chunks' loads are in flight (32 + 16 + 1 VGPRs per chunk).  Wave w of W takes the CONTIGUOUS chunk range
-// [w * chunks / W, (w + 1) * chunks / W): a function of the shape alone, and one that keeps a wave inside as few K blocks as possible.
+// convert), and ONE 16 B-per-lane load of the chunk's 128 activations with the masked K-steps of gptqhip_moe_common.h.  Up to four chunks' loads
+// are in flight (32 + 16 + 1 VGPRs per chunk).  Wave w of W takes the CONTIGUOUS chunk range [w * chunks / W, (w + 1) * chunks / W): a function
+// of the shape alone, and one that keeps a wave inside as few K blocks as possible.
 //
 // SCALES (reciprocals, formed once by gptqhip_fp8_repack).  gate|up carries one scale row per fused column: [E, 2I] or [E, 2I, H / bc]; down is
 // [E] | [E, H] | [E, H / br, I / bc].  With K-block scales the fp32 accumulator is multiplied by the reciprocal scale and flushed at every bc
@@ -26,17 +23,10 @@
 //
 // Expert ids outside [0, E) dereference nothing: the slot contributes zero (gate_up writes zeros for it) and the device status word is set to 1.
 // NaN codes (0x7f, 0xff) are undefined, as in gptqhip_fp8.hip.  LDS: 16 x 16 floats; no floating-point atomics: two runs give the same bits.
-#include "../../include/gptqhip.h"
-#include "gptqhip_device.h"
 #include "gptqhip_fp8_frag.h"
-#include "gptqhip_host.h"
+#include "gptqhip_moe_common.h"
 
 namespace gptqhip {
-
-constexpr int kMoeFp8MaxRows = 16;      // tokens per call, and slots per token
-constexpr int kMoeFp8GateUpWaves = 8;   // most waves of a gate_up block (in-block split of K)
-constexpr int kMoeFp8DownWaves = 16;    // most waves of a down block
-constexpr int kMoeFp8Ahead = 4;         // chunks whose loads a wave issues before consuming the first
 
 struct MoeFp8Params {
     const uint16_t* x;       // gate_up: [T, H]; down: act [T * top_k, I]
@@ -62,16 +52,15 @@ __device__ __forceinline__ float fp8_wave_partial(const uint8_t* __restrict__ wt
                                                   int c0, int c1, int cpb, int lane) {
     const int c16 = lane & 15, rq = lane >> 4;
     uint32_t mask[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) mask[j] = (c16 & 3) == j ? 0xffffffffu : 0u;
+    moe_kstep_masks(c16, mask);
     const uint16_t* xl = xrow + 32 * (c16 & 3) + 8 * rq;
     const f4_t zero = {0.f, 0.f, 0.f, 0.f};
     f4_t acc = zero, tot = zero;
-    for (int base = c0; base < c1; base += kMoeFp8Ahead) {
-        u4_t w[kMoeFp8Ahead][2], a[kMoeFp8Ahead];
-        float r[kMoeFp8Ahead];
+    for (int base = c0; base < c1; base += kMoeAhead) {
+        u4_t w[kMoeAhead][2], a[kMoeAhead];
+        float r[kMoeAhead];
 #pragma unroll
-        for (int u = 0; u < kMoeFp8Ahead; ++u) {
+        for (int u = 0; u < kMoeAhead; ++u) {
             const int ck = base + u < c1 ? base + u : c1 - 1;   // past the end: a harmless repeat of the wave's last chunk
             w[u][0] = __builtin_nontemporal_load(reinterpret_cast<const u4_t*>(wt + (size_t)ck * kFp8BlockBytes));
             w[u][1] = __builtin_nontemporal_load(reinterpret_cast<const u4_t*>(wt + (size_t)ck * kFp8BlockBytes + 1024));
@@ -79,19 +68,14 @@ __device__ __forceinline__ float fp8_wave_partial(const uint8_t* __restrict__ wt
             r[u] = BLOCK ? rs[ck / cpb] : 0.f;
         }
 #pragma unroll
-        for (int u = 0; u < kMoeFp8Ahead; ++u) {
+        for (int u = 0; u < kMoeAhead; ++u) {
             const int ck = base + u;
             if (ck < c1) {   // wave-uniform
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    u4_t aj;
-                    aj.x = a[u].x & mask[j];
-                    aj.y = a[u].y & mask[j];
-                    aj.z = a[u].z & mask[j];
-                    aj.w = a[u].w & mask[j];
                     const u4_t& wh = w[u][j >> 1];   // K-step j = 2 h + jj: half h, bytes 8 jj .. 8 jj + 7 of the lane's 16
                     const u4_t b = (j & 1) ? fp8x8_to_frag<ACT, kCvtPacked>(wh.z, wh.w) : fp8x8_to_frag<ACT, kCvtPacked>(wh.x, wh.y);
-                    acc = mfma16<ACT>(aj, b, acc);
+                    acc = mfma16<ACT>(moe_masked_a(a[u], mask[j]), b, acc);
                 }
                 if (BLOCK && ((ck + 1) % cpb == 0 || ck + 1 == c1)) {   // the K block (or the wave's share of it) ends here
                     tot += acc * r[u];
@@ -100,23 +84,18 @@ __device__ __forceinline__ float fp8_wave_partial(const uint8_t* __restrict__ wt
             }
         }
     }
-    // accumulator register i of lanes 0 .. 15 = row i = K-step i's share
-    const f4_t s = BLOCK ? tot : acc;
-    return rq == 0 ? (s[0] + s[1]) + (s[2] + s[3]) : 0.f;
+    return moe_lane_sum(BLOCK ? tot : acc, rq);
 }
 
 template <int ACT, bool BLOCK>
-__global__ __launch_bounds__(64 * kMoeFp8GateUpWaves) void moe_fp8_gate_up_kernel(MoeFp8Params p) {
-    __shared__ float red[kMoeFp8GateUpWaves][16];
+__global__ __launch_bounds__(64 * kMoeGateUpWaves) void moe_fp8_gate_up_kernel(MoeFp8Params p) {
+    __shared__ float red[kMoeGateUpWaves][16];
     const int tile = blockIdx.x, slot = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
     const int inter = p.N >> 1;
     const int e = p.ids[slot];
-    if (e < 0 || e >= p.E) {   // block-uniform
-        if (threadIdx.x < 8) p.out[(size_t)slot * inter + tile * 8 + threadIdx.x] = 0;
-        if (threadIdx.x == 0) *p.status = 1;
-        return;
-    }
+    uint16_t* out8 = p.out + (size_t)slot * inter + tile * 8;
+    if (moe_gate_up_invalid(e, p.E, out8, p.status)) return;
     const int n = tile * kTileN + (lane & 15);
     const uint8_t* wt = p.wt + (size_t)e * p.w_stride + (size_t)tile * p.chunks * kFp8BlockBytes + lane * 16;
     const float* rs = p.rs + (size_t)e * p.s_stride + (size_t)n * p.kbn;   // row scales: kbn = 1, one scale per column
@@ -129,11 +108,8 @@ __global__ __launch_bounds__(64 * kMoeFp8GateUpWaves) void moe_fp8_gate_up_kerne
     float v = 0.f;
     for (int w = 0; w < W; ++w) v += red[w][lane & 15];   // wave order, always
     if (!BLOCK) v *= rs[0];
-    // lanes 0 .. 7 hold gate columns, lanes 8 .. 15 the matching up columns: HF's act_fn(gate) * up, every step rounded in the activation dtype
-    const float y = round_through<ACT>(v);
-    const float up = __shfl_down(y, 8);
-    const float a = round_through<ACT>(y / (1.0f + expf(-y))) * up;   // expf, not __expf: HF evaluates SiLU with the accurate exp
-    if (lane < 8) p.out[(size_t)slot * inter + tile * 8 + lane] = f32_to_16<ACT>(a);
+    const uint16_t a = moe_silu_up<ACT>(v);   // lanes 0 .. 7 hold gate columns, lanes 8 .. 15 the matching up columns
+    if (lane < 8) out8[lane] = a;
 }
 
 // float offset of (expert's) scale for column n of the down projection, tensor / row layouts
@@ -142,8 +118,8 @@ __device__ __forceinline__ size_t down_scale_index(const MoeFp8Params& p, int e,
 }
 
 template <int ACT, bool BLOCK>
-__global__ __launch_bounds__(64 * kMoeFp8DownWaves) void moe_fp8_down_kernel(MoeFp8Params p) {
-    __shared__ float red[kMoeFp8DownWaves][16];
+__global__ __launch_bounds__(64 * kMoeDownWaves) void moe_fp8_down_kernel(MoeFp8Params p) {
+    __shared__ float red[kMoeDownWaves][16];
     const int tile = blockIdx.x, t = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = wave / p.wps, sub = wave - j * p.wps;   // this wave's slot and its share of the slot's chunks
@@ -161,17 +137,9 @@ __global__ __launch_bounds__(64 * kMoeFp8DownWaves) void moe_fp8_down_kernel(Moe
     }
     if (lane < 16) red[wave][lane] = part;
     __syncthreads();
-    if (wave != 0 || lane >= 16) return;
-    float y = 0.f;
-    for (int jj = 0; jj < p.top_k; ++jj) {   // slot order; an out-of-range expert contributes nothing, whatever its routing weight
-        const int ej = p.ids[t * p.top_k + jj];
-        if (ej < 0 || ej >= p.E) continue;
-        float d = 0.f;
-        for (int s = 0; s < p.wps; ++s) d += red[jj * p.wps + s][lane];
-        if (!BLOCK) d *= p.rs[down_scale_index(p, ej, n)];
-        y += p.weights[t * p.top_k + jj] * d;
-    }
-    p.out[(size_t)t * p.N + n] = f32_to_16<ACT>(y);
+    // block scales are already in the partial sums; tensor / row scales multiply each slot's reduced dot product
+    moe_combine_slots<ACT>(red, wave, lane, p.ids + t * p.top_k, p.weights + t * p.top_k, p.top_k, p.E, p.wps, p.out + (size_t)t * p.N + tile * kTileN,
+                           [&](float d, int ej) { return BLOCK ? d : d * p.rs[down_scale_index(p, ej, n)]; });
 }
 
 // the scale layout of one stacked projection [N, K]: nullptr when served
@@ -184,38 +152,15 @@ static const char* moe_fp8_scale_error(int K, int N, int mode, int br, int bc) {
 }
 
 static bool moe_fp8_dims_ok(int H, int I, int T, int top_k) {
-    return H > 0 && I > 0 && H % 128 == 0 && I % 128 == 0 && T >= 1 && T <= kMoeFp8MaxRows && top_k >= 1 && top_k <= kMoeFp8MaxRows;
+    return H > 0 && I > 0 && H % 128 == 0 && I % 128 == 0 && moe_few_tokens_ok(T, top_k);
 }
 
 // K, N, mode, br, bc: the projection the call runs
 static int moe_fp8_validate(const char* fn, const void* const* ptrs16, int n16, const void* const* ptrs4, int n4, int T, int top_k, int E, int H, int I,
                             int K, int N, int mode, int br, int bc, int act_dtype) {
-    for (int i = 0; i < n16 + n4; ++i) {
-        if ((i < n16 ? ptrs16[i] : ptrs4[i - n16]) == nullptr) {
-            set_error("%s: null tensor pointer", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    for (int i = 0; i < n16; ++i) {
-        if (reinterpret_cast<uintptr_t>(ptrs16[i]) % 16 != 0) {
-            set_error("%s: activations, weights and outputs must be 16-byte aligned", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    for (int i = 0; i < n4; ++i) {
-        if (reinterpret_cast<uintptr_t>(ptrs4[i]) % 4 != 0) {
-            set_error("%s: reciprocal scales, ids, routing weights and status must be 4-byte aligned", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    if (T < 1 || T > kMoeFp8MaxRows || top_k < 1 || top_k > kMoeFp8MaxRows) {
-        set_error("%s: T=%d and top_k=%d must be 1..%d", fn, T, top_k, kMoeFp8MaxRows);
-        return GPTQHIP_EINVAL;
-    }
-    if (E < 1) {
-        set_error("%s: E=%d experts", fn, E);
-        return GPTQHIP_EINVAL;
-    }
+    int rc = moe_check_ptrs(fn, ptrs16, n16, "activations, weights and outputs", ptrs4, n4, "reciprocal scales, ids, routing weights and status");
+    if (!rc) rc = moe_check_few_tokens(fn, T, top_k, E);
+    if (rc) return rc;
     if (H <= 0 || I <= 0 || H % 128 != 0 || I % 128 != 0) {
         set_error("%s: unsupported shape H=%d I=%d (H and I positive multiples of 128)", fn, H, I);
         return GPTQHIP_EINVAL;
@@ -279,7 +224,7 @@ int gptqhip_moe_fp8_gate_up(const void* x, const uint8_t* weight_t, const float*
     int rc = moe_fp8_validate("gptqhip_moe_fp8_gate_up", p16, 3, p4, 3, T, top_k, E, H, I, H, 2 * I, mode, 1, block_cols, act_dtype);
     if (rc) return rc;
     const MoeFp8Params p = moe_fp8_params(x, weight_t, rscale, ids, nullptr, act, status, top_k, E, H, 2 * I, mode, 1, block_cols);
-    const int waves = p.chunks < kMoeFp8GateUpWaves ? p.chunks : kMoeFp8GateUpWaves;
+    const int waves = p.chunks < kMoeGateUpWaves ? p.chunks : kMoeGateUpWaves;
     const dim3 grid(2 * I / kTileN, T * top_k), block(64 * waves);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool blk = mode == GPTQHIP_FP8_SCALE_BLOCK;
@@ -301,7 +246,7 @@ int gptqhip_moe_fp8_down(const void* act, const uint8_t* weight_t, const float* 
     int rc = moe_fp8_validate("gptqhip_moe_fp8_down", p16, 3, p4, 4, T, top_k, E, H, I, I, H, scale_mode, block_rows, block_cols, act_dtype);
     if (rc) return rc;
     MoeFp8Params p = moe_fp8_params(act, weight_t, rscale, ids, weights, out, status, top_k, E, I, H, scale_mode, block_rows, block_cols);
-    const int per_slot = kMoeFp8DownWaves / top_k;
+    const int per_slot = kMoeDownWaves / top_k;
     p.wps = p.chunks < per_slot ? p.chunks : per_slot;
     const dim3 grid(H / kTileN, T), block(64 * p.wps * top_k);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

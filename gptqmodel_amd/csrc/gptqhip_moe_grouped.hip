@@ -14,15 +14,13 @@
 //                        stores nothing), the B fragments are dequant_word4 of the tiled words of expert unit_expert[u].  The block's waves split
 //                        the 128-row chunks (wave w takes w, w + W, ..), park their 16 x 16 fp32 accumulators in LDS and threads 0 .. 255 add them
 //                        in wave order.  Rows of a unit never mix, and W depends on the shape alone: a token's bits do not depend on its batch.
-//                          GATE_UP: the rounding chain of GPTQHIP_OUT_SILU_MUL_PAIRED, scattered to act[slot, 8 tile .. 8 tile + 8)
+//                          GATE_UP: the SiLU * up rounding chain (gptqhip_moe_common.h: moe_silu_up), scattered to act[slot, 8 tile .. 8 tile + 8)
 //                          DOWN:    the unrounded fp32 dot products, scattered to part[slot, 16 tile .. 16 tile + 16)
 //   moe_combine_kernel   out[t, n] = act( sum_j weights[t, j] * part[t * top_k + j, n] ), fp32, slot order, ONE rounding, ids outside [0, E) skipped:
-//                        the numerics contract of moe_down_kernel.  No floating-point atomics anywhere.
+//                        the combine contract of gptqhip_moe_common.h on 4-wide vectors.  No floating-point atomics anywhere.
 //
 // Registers / LDS / scratch per kernel: DESIGN.md 4.4.
-#include "../../include/gptqhip.h"
-#include "gptqhip_device.h"
-#include "gptqhip_host.h"
+#include "gptqhip_moe_common.h"
 
 namespace gptqhip {
 
@@ -184,11 +182,8 @@ __global__ __launch_bounds__(64 * MAXW) void moe_grouped_kernel(GroupedParams p)
         for (int ww = 0; ww < W; ++ww) v += red[ww][mrow][n];
         const int s = slots[mrow];
         if constexpr (GATE_UP) {
-            // columns 0 .. 7 are gate columns, 8 .. 15 the matching up columns: HF's act_fn(gate) * up, every step rounded in the activation dtype
-            const float y = round_through<ACT>(v);
-            const float up = __shfl_down(y, 8);
-            const float r = round_through<ACT>(y / (1.0f + expf(-y))) * up;   // expf, not __expf: HF evaluates SiLU with the accurate exp
-            if (n < 8 && s >= 0) reinterpret_cast<uint16_t*>(p.out)[(size_t)s * (p.N >> 1) + tile * 8 + n] = f32_to_16<ACT>(r);
+            const uint16_t r = moe_silu_up<ACT>(v);   // columns 0 .. 7 are gate columns, 8 .. 15 the matching up columns
+            if (n < 8 && s >= 0) reinterpret_cast<uint16_t*>(p.out)[(size_t)s * (p.N >> 1) + tile * 8 + n] = r;
         } else {
             if (s >= 0) reinterpret_cast<float*>(p.out)[(size_t)s * p.N + tile * 16 + n] = v;
         }
@@ -235,36 +230,13 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(CombineParams p) {
     *reinterpret_cast<u2_t*>(p.out + (size_t)t * p.H + col) = o;
 }
 
-static bool grouped_group_ok(int K, int group_size) {   // 128 * 2^n dividing K (one group for the whole K included)
-    if (group_size < 128 || K % group_size != 0) return false;
-    const int q = group_size / 128;
-    return group_size % 128 == 0 && (q & (q - 1)) == 0;
-}
-
 static bool grouped_routing_ok(int T, int top_k, int E) {
     return T >= 1 && top_k >= 1 && top_k <= kGroupedMaxTopK && E >= 1 && E <= kGroupedMaxExperts && (long long)T * top_k <= kGroupedMaxSlots;
 }
 
 static int grouped_check_ptrs(const char* fn, const void* const* ptrs16, int n16, const void* const* ptrs4, int n4) {
-    for (int i = 0; i < n16 + n4; ++i) {
-        if ((i < n16 ? ptrs16[i] : ptrs4[i - n16]) == nullptr) {
-            set_error("%s: null tensor pointer", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    for (int i = 0; i < n16; ++i) {
-        if (reinterpret_cast<uintptr_t>(ptrs16[i]) % 16 != 0) {
-            set_error("%s: activations, weights, constants, partial sums and outputs must be 16-byte aligned", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    for (int i = 0; i < n4; ++i) {
-        if (reinterpret_cast<uintptr_t>(ptrs4[i]) % 4 != 0) {
-            set_error("%s: ids, weights, sort buffers and status must be 4-byte aligned", fn);
-            return GPTQHIP_EINVAL;
-        }
-    }
-    return GPTQHIP_OK;
+    return moe_check_ptrs(fn, ptrs16, n16, "activations, weights, constants, partial sums and outputs", ptrs4, n4,
+                          "ids, weights, sort buffers and status");
 }
 
 static int grouped_check_routing(const char* fn, int T, int top_k, int E) {
@@ -276,32 +248,11 @@ static int grouped_check_routing(const char* fn, int T, int top_k, int E) {
     return GPTQHIP_OK;
 }
 
-static int grouped_check_dtypes(const char* fn, int act_dtype, int scale_dtype) {
-    if ((act_dtype != GPTQHIP_FP16 && act_dtype != GPTQHIP_BF16) || (scale_dtype != GPTQHIP_FP16 && scale_dtype != GPTQHIP_BF16) ||
-        (act_dtype == GPTQHIP_BF16 && scale_dtype == GPTQHIP_FP16)) {
-        set_error("%s: unsupported dtypes act=%d scales=%d (fp16 x fp16, bf16 x bf16, fp16 activations x bf16 scales)", fn, act_dtype, scale_dtype);
-        return GPTQHIP_EINVAL;
-    }
-    return GPTQHIP_OK;
-}
-
-static int grouped_check_shape(const char* fn, int H, int I, int K, int group_size, int bits) {
-    if (bits != 4 || H <= 0 || I <= 0 || H % 128 != 0 || I % 128 != 0 || !grouped_group_ok(K, group_size)) {
-        set_error("%s: unsupported shape H=%d I=%d group_size=%d bits=%d (4 bits, H and I multiples of 128, group_size = 128 * 2^n dividing K=%d)",
-                  fn, H, I, group_size, bits, K);
-        return GPTQHIP_EINVAL;
-    }
-    return GPTQHIP_OK;
-}
-
 template <bool GATE_UP, int MAXW>
 static void grouped_launch(int act_dtype, int scale_dtype, const GroupedParams& p, dim3 grid, dim3 block, hipStream_t stream) {
-    if (act_dtype == GPTQHIP_FP16 && scale_dtype == GPTQHIP_FP16)
-        hipLaunchKernelGGL((moe_grouped_kernel<kFP16, kFP16, GATE_UP, MAXW>), grid, block, 0, stream, p);
-    else if (act_dtype == GPTQHIP_BF16)
-        hipLaunchKernelGGL((moe_grouped_kernel<kBF16, kBF16, GATE_UP, MAXW>), grid, block, 0, stream, p);
-    else
-        hipLaunchKernelGGL((moe_grouped_kernel<kFP16, kBF16, GATE_UP, MAXW>), grid, block, 0, stream, p);
+    moe_dispatch(act_dtype, scale_dtype, [&](auto a, auto s) {
+        hipLaunchKernelGGL((moe_grouped_kernel<decltype(a)::value, decltype(s)::value, GATE_UP, MAXW>), grid, block, 0, stream, p);
+    });
 }
 
 static GroupedParams grouped_params(const void* x, const uint32_t* qw, const uint32_t* meta, const int32_t* sorted_slots, const int32_t* unit_expert,
@@ -337,8 +288,8 @@ extern "C" {
 int gptqhip_moe_grouped_supported(int H, int I, int group_size, int bits, int has_perm, int T, int top_k, int E) {
     if (has_perm) return 0;
     // group_size <= 0: one group for the whole K of each projection (group_size = -1 checkpoints)
-    return bits == 4 && H > 0 && I > 0 && H % 128 == 0 && I % 128 == 0 && grouped_group_ok(H, group_size <= 0 ? H : group_size) &&
-                   grouped_group_ok(I, group_size <= 0 ? I : group_size) && grouped_routing_ok(T, top_k, E)
+    return moe_int4_shape_ok(H, I, H, group_size <= 0 ? H : group_size, bits) && moe_int4_shape_ok(H, I, I, group_size <= 0 ? I : group_size, bits) &&
+                   grouped_routing_ok(T, top_k, E)
                ? 1
                : 0;
 }
@@ -375,8 +326,8 @@ int gptqhip_moe_gate_up_grouped(const void* x, const uint32_t* qweight_t, const 
     const void* p4[] = {sorted_slots, unit_expert, num_units};
     int rc = grouped_check_ptrs(fn, p16, 4, p4, 3);
     if (!rc) rc = grouped_check_routing(fn, T, top_k, E);
-    if (!rc) rc = grouped_check_shape(fn, H, I, H, group_size, bits);
-    if (!rc) rc = grouped_check_dtypes(fn, act_dtype, scale_dtype);
+    if (!rc) rc = moe_check_int4_shape(fn, H, I, H, group_size, bits);
+    if (!rc) rc = moe_check_dtypes(fn, act_dtype, scale_dtype);
     if (rc) return rc;
     const GroupedParams p = grouped_params(x, qweight_t, meta, sorted_slots, unit_expert, num_units, act, T * top_k, top_k, E, H, 2 * I, group_size);
     const int waves = p.chunks < kGroupedGateUpWaves ? p.chunks : kGroupedGateUpWaves;
@@ -393,8 +344,8 @@ int gptqhip_moe_down_grouped(const void* act, const uint32_t* qweight_t, const u
     const void* p4[] = {sorted_slots, unit_expert, num_units};
     int rc = grouped_check_ptrs(fn, p16, 4, p4, 3);
     if (!rc) rc = grouped_check_routing(fn, T, top_k, E);
-    if (!rc) rc = grouped_check_shape(fn, H, I, I, group_size, bits);
-    if (!rc) rc = grouped_check_dtypes(fn, act_dtype, scale_dtype);
+    if (!rc) rc = moe_check_int4_shape(fn, H, I, I, group_size, bits);
+    if (!rc) rc = moe_check_dtypes(fn, act_dtype, scale_dtype);
     if (rc) return rc;
     const GroupedParams p = grouped_params(act, qweight_t, meta, sorted_slots, unit_expert, num_units, part, T * top_k, 1, E, I, H, group_size);
     const int waves = p.chunks < kGroupedDownWaves ? p.chunks : kGroupedDownWaves;

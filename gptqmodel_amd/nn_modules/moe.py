@@ -7,12 +7,10 @@ call signature of transformers' experts modules (Qwen3MoeExperts.forward / Mixtr
 
     forward(hidden_states [T, H], top_k_index [T, k], top_k_weights [T, k]) -> [T, H]
 
-* fast path (ops.moe_supported: 4 bits, group_size = 128 * 2^n, no act-order, T <= 16, top_k <= 16): gptqhip_moe_gate_up + gptqhip_moe_down,
-  two launches into persistent buffers with the routing left on the device -- no host synchronisation, safe inside torch.cuda.graph.  An
-  expert id outside [0, E) contributes zero and sets a device status word, which check_status() reads (never forward()).
-  Rounding: per-weight rounding and the SiLU chain are the reference's; the top_k expert outputs are combined in ONE fp32 weighted sum in
-  slot order and rounded once (include/gptqhip.h), where the HF loop rounds every expert's output and every product and accumulates in the
-  activation dtype.
+The call checks, the device-routed fast path, the status word and the host-routed slow path are StackedMoeExperts' (nn_modules/moe_base.py, which
+states the rounding contract); this module adds the 4-bit stacking and:
+
+* fast path (ops.moe_supported: 4 bits, group_size = 128 * 2^n, no act-order, T <= 16, top_k <= 16): gptqhip_moe_gate_up + gptqhip_moe_down.
 * grouped path (ops.moe_grouped_supported: the same shapes at ANY T): gptqhip_moe_align + gptqhip_moe_gate_up_grouped + gptqhip_moe_down_grouped
   + gptqhip_moe_combine -- the slots sorted by expert on the device, every 16-row unit of one expert on the matrix pipe, the same combine
   contract (one fp32 weighted sum in slot order, one rounding), the same status word, no host synchronisation.  Taken when `grouped_routing`
@@ -24,15 +22,15 @@ call signature of transformers' experts modules (Qwen3MoeExperts.forward / Mixtr
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from ..utils.model import deinterleave_gate_up, fuse_gate_up_interleaved
+from ..utils.model import fuse_gate_up_interleaved
+from .moe_base import MAX_FAST_TOKENS, StackedMoeExperts
 
-MAX_FAST_TOKENS = 16
 # eager window of the grouped path when grouped_routing is set.  NOT measured yet: the first T the ungrouped ops do not serve,
 # and the ops' slot limit; tests/dev/moe_grouped_probe.py prints the values the measurement rule gives.
 GROUPED_MIN_TOKENS = 17
@@ -51,33 +49,17 @@ def _interleave_tiled(gate: torch.Tensor, up: torch.Tensor, tiles: int, inner: i
     return out.view(-1)
 
 
-def _is_hip_gptq(m) -> bool:
-    return getattr(m, "_GPTQHIP_KERNEL_CLASS", False) and getattr(m, "QUANT_TYPE", "") == "hip_gptq"
+class HipMoeExperts(StackedMoeExperts):
+    _SOURCE_KIND = "HIP GPTQ linear"
+    _RELEASE_NAMES = ("qweight", "qzeros", "scales", "g_idx", "meta")
 
-
-def _release(m) -> None:
-    """Drop a per-expert module's device tensors once they are stacked."""
-    for name in ("qweight", "qzeros", "scales", "g_idx", "meta"):
-        t = getattr(m, name, None)
-        if isinstance(t, torch.Tensor):
-            t.data = torch.empty(0, dtype=t.dtype, device=t.device)
-    m._ready = False
-
-
-class HipMoeExperts(nn.Module):
     def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, gate_up_group_size: int, down_group_size: int,
                  scale_dtype: torch.dtype):
-        super().__init__()
-        self.num_experts = num_experts
-        self.hidden_dim = hidden_dim
-        self.intermediate_dim = intermediate_dim
+        super().__init__(num_experts, hidden_dim, intermediate_dim)
         self.gate_up_group_size = gate_up_group_size
         self.down_group_size = down_group_size
         self.scale_dtype = scale_dtype
         self.bits = 4
-        self.training = False
-        self._scratch: Dict[Tuple, Tuple[torch.Tensor, ...]] = {}
-        self._fast_ok: Dict[Tuple[int, int], bool] = {}
         self.grouped_routing = os.environ.get("GPTQHIP_MOE_GROUPED", "0") == "1"
         self.grouped_min_tokens = GROUPED_MIN_TOKENS
         self.grouped_max_tokens = GROUPED_MAX_TOKENS
@@ -85,10 +67,9 @@ class HipMoeExperts(nn.Module):
         self._grouped_eager: Dict[Tuple, Dict] = {}        # (dtype, device) -> one grow-only buffer set, sliced per call
         self._grouped_captured: Dict[Tuple, Tuple[torch.Tensor, ...]] = {}      # (T, top_k, dtype, device) -> buffers a graph holds: never freed
 
-    def train(self, mode: bool = True):
-        if mode:      # the quantised linears it is built from refuse training mode the same way (SUPPORTS_TRAINING = False)
-            raise NotImplementedError("HipMoeExperts: inference only (the HIP quant kernels have no backward)")
-        return super().train(False)
+    @staticmethod
+    def _is_source(m) -> bool:
+        return getattr(m, "_GPTQHIP_KERNEL_CLASS", False) and getattr(m, "QUANT_TYPE", "") == "hip_gptq"
 
     def extra_repr(self) -> str:
         return (f"experts={self.num_experts}, hidden={self.hidden_dim}, intermediate={self.intermediate_dim}, bits=4, "
@@ -102,20 +83,12 @@ class HipMoeExperts(nn.Module):
         the column interleave of fuse_gate_up_interleaved, all experts are stacked into two contiguous buffers per projection, and the
         per-expert copies are released as they are stacked (peak extra memory: one expert).  Raises NotImplementedError when the experts
         cannot share the stacked layout; nothing has been modified then."""
-        gate, up, down = list(gate), list(up), list(down)
-        E = len(gate)
-        if E == 0 or len(up) != E or len(down) != E:
-            raise NotImplementedError("from_linears needs three equal-length, non-empty lists")
-        g0, d0 = gate[0], down[0]
+        gate, up, down = cls._check_lists(gate, up, down)
+        E, g0, d0 = len(gate), gate[0], down[0]
         H, I = g0.in_features, g0.out_features
         for e in range(E):
             for m, (k, n) in ((gate[e], (H, I)), (up[e], (H, I)), (down[e], (I, H))):
-                if not _is_hip_gptq(m):
-                    raise NotImplementedError(f"expert {e}: {type(m).__name__} is not a HIP GPTQ linear")
-                if getattr(m, "adapter", None) is not None or m.bias is not None:
-                    raise NotImplementedError(f"expert {e}: adapters / biases are not carried by the stacked experts")
-                if (m.in_features, m.out_features) != (k, n):
-                    raise NotImplementedError(f"expert {e}: shape {(m.in_features, m.out_features)} != {(k, n)}")
+                cls._check_module(e, m, k, n)
                 if m.bits != 4 or getattr(m, "planar", False):
                     raise NotImplementedError(f"expert {e}: {m.bits}-bit codes (4-bit only)")
                 if m.scales.dtype != g0.scales.dtype or m.group_size != (g0 if k == H else d0).group_size or m._ready != g0._ready:
@@ -152,7 +125,7 @@ class HipMoeExperts(nn.Module):
                 down[e].post_init()
             bufs[2][e], bufs[3][e] = down[e].qweight.data, down[e].meta
             for m in (gate[e], up[e], down[e]):
-                _release(m)
+                cls._release(m)
         for name, t in zip(("gate_up_qweight", "gate_up_meta", "down_qweight", "down_meta"), bufs):
             self.register_buffer(name, t, persistent=False)
         self.register_buffer("status", torch.zeros(1, dtype=torch.int32, device=dev), persistent=False)
@@ -164,12 +137,13 @@ class HipMoeExperts(nn.Module):
         key = (T, top_k)
         ok = self._fast_ok.get(key)
         if ok is None:
-            gs = self.gate_up_group_size
-            if gs != self.down_group_size:      # one group for the whole K of each projection (group_size = -1), or not servable
-                gs = -1 if (gs == self.hidden_dim and self.down_group_size == self.intermediate_dim) else 0
+            gs = self._common_group_size()
             ok = gs != 0 and ops.moe_supported(self.hidden_dim, self.intermediate_dim, gs, self.bits, False, T, top_k)
             self._fast_ok[key] = ok
-        return ok and dtype in (torch.float16, torch.bfloat16) and not (dtype == torch.bfloat16 and self.scale_dtype == torch.float16)
+        return ok and self._dtype_ok(dtype)
+
+    def _dtype_ok(self, dtype: torch.dtype) -> bool:
+        return dtype in (torch.float16, torch.bfloat16) and not (dtype == torch.bfloat16 and self.scale_dtype == torch.float16)
 
     def _common_group_size(self) -> int:
         """The one group_size argument of the shape predicates: -1 = one group for the whole K of each projection, 0 = not servable."""
@@ -187,7 +161,7 @@ class HipMoeExperts(nn.Module):
             gs = self._common_group_size()
             ok = gs != 0 and ops.moe_grouped_supported(self.hidden_dim, self.intermediate_dim, gs, self.bits, False, T, top_k, self.num_experts)
             self._grouped_ok[key] = ok
-        return ok and dtype in (torch.float16, torch.bfloat16) and not (dtype == torch.bfloat16 and self.scale_dtype == torch.float16)
+        return ok and self._dtype_ok(dtype)
 
     def _grouped_alloc(self, S: int, T: int, dtype: torch.dtype, device: torch.device) -> Dict:
         units = ops.moe_grouped_units(S, self.num_experts)
@@ -219,17 +193,7 @@ class HipMoeExperts(nn.Module):
         T, top_k = top_k_index.shape
         S, H, I, E = T * top_k, self.hidden_dim, self.intermediate_dim, self.num_experts
         b = self._grouped_scratch(T, top_k, hidden_states.dtype, hidden_states.device, capturing)
-        if top_k_index.dtype == torch.int32 and top_k_index.is_contiguous():
-            ids = top_k_index
-        else:
-            ids = b["ids"][:S].view(T, top_k)
-            ids.copy_(top_k_index)
-        if top_k_weights.dtype == torch.float32 and top_k_weights.is_contiguous():
-            w = top_k_weights
-        else:
-            w = b["w"][:S].view(T, top_k)
-            w.copy_(top_k_weights)
-        x = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
+        x, ids, w = self._device_routing(hidden_states, top_k_index, top_k_weights, b["ids"], b["w"])
         act, part, out = b["act"][:S * I].view(S, I), b["part"][:S * H].view(S, H), b["out"][:T * H].view(T, H)
         ops.moe_align(ids, b["sorted"], b["unit_expert"], b["num_units"], self.status, E)
         ops.moe_gate_up_grouped(x, self.gate_up_qweight, self.gate_up_meta, b["sorted"], b["unit_expert"], b["num_units"], act, top_k, E, I,
@@ -239,80 +203,26 @@ class HipMoeExperts(nn.Module):
         ops.moe_combine(part, ids, w, out, self.status, E)
         return out
 
-    def _scratch_for(self, T: int, top_k: int, dtype: torch.dtype, device: torch.device):
-        key = (T, top_k, dtype)
-        s = self._scratch.get(key)
-        if s is None or s[0].device != device:
-            s = (torch.empty((T * top_k, self.intermediate_dim), dtype=dtype, device=device),
-                 torch.empty((T, self.hidden_dim), dtype=dtype, device=device),
-                 torch.empty((T, top_k), dtype=torch.int32, device=device),
-                 torch.empty((T, top_k), dtype=torch.float32, device=device))
-            self._scratch[key] = s
-        return s
-
-    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
-        if hidden_states.dim() != 2 or hidden_states.shape[1] != self.hidden_dim or top_k_index.dim() != 2 \
-                or top_k_index.shape != top_k_weights.shape or top_k_index.shape[0] != hidden_states.shape[0]:
-            raise RuntimeError(f"HipMoeExperts: expected hidden_states [T, {self.hidden_dim}] and top_k_index / top_k_weights [T, k], got "
-                               f"{tuple(hidden_states.shape)}, {tuple(top_k_index.shape)}, {tuple(top_k_weights.shape)}")
-        if not hidden_states.is_cuda:
-            raise RuntimeError("gptqmodel_amd HIP ops need tensors on a ROCm device (got a CPU tensor); there is no CPU fallback")
+    def _forward_routed(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
         T, top_k = top_k_index.shape
-        if T == 0:
-            return torch.zeros_like(hidden_states)
         if self.grouped_routing and self.grouped_min_tokens <= T <= self.grouped_max_tokens and self.grouped_path(T, top_k, hidden_states.dtype):
             return self._forward_grouped(hidden_states, top_k_index, top_k_weights, torch.cuda.is_current_stream_capturing())
         if T > MAX_FAST_TOKENS and torch.cuda.is_current_stream_capturing() and self.grouped_path(T, top_k, hidden_states.dtype):
             return self._forward_grouped(hidden_states, top_k_index, top_k_weights, True)      # the host-routed loop cannot be captured
-        if T > MAX_FAST_TOKENS or not self.fast_path(T, top_k, hidden_states.dtype):
-            return self._forward_loop(hidden_states, top_k_index, top_k_weights)
-        # the result lives in a persistent buffer of this module (one per (T, top_k, dtype)): the next call with that signature overwrites it
-        act, out, ids, w = self._scratch_for(T, top_k, hidden_states.dtype, hidden_states.device)
-        if top_k_index.dtype == torch.int32 and top_k_index.is_contiguous():
-            ids = top_k_index
-        else:
-            ids.copy_(top_k_index)
-        if top_k_weights.dtype == torch.float32 and top_k_weights.is_contiguous():
-            w = top_k_weights
-        else:
-            w.copy_(top_k_weights)
-        x = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
+        return super()._forward_routed(hidden_states, top_k_index, top_k_weights)
+
+    def _fused_gate_up(self, x: torch.Tensor, ids: torch.Tensor, act: torch.Tensor) -> None:
         ops.moe_gate_up(x, self.gate_up_qweight, self.gate_up_meta, ids, act, self.status, self.num_experts, self.intermediate_dim,
                         self.gate_up_group_size, self.scale_dtype)
-        ops.moe_down(act, self.down_qweight, self.down_meta, ids, w, out, self.status, self.num_experts, self.down_group_size,
-                     self.scale_dtype)
-        return out
 
-    def check_status(self) -> None:
-        """Host read of the device status word (a synchronisation: call it outside the decode loop).  Raises IndexError when a fast-path or
-        grouped-path call since the last check met an expert id outside [0, num_experts) -- that slot contributed zero -- and clears the word."""
-        if int(self.status.item()) != 0:
-            self.status.zero_()
-            raise IndexError(f"HipMoeExperts: expert index out of range [0, {self.num_experts}) in a fused MoE call")
+    def _fused_down(self, act: torch.Tensor, ids: torch.Tensor, w: torch.Tensor, out: torch.Tensor) -> None:
+        ops.moe_down(act, self.down_qweight, self.down_meta, ids, w, out, self.status, self.num_experts, self.down_group_size, self.scale_dtype)
 
-    def _forward_loop(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
-        """The experts loop of the HF module (host-routed) on ops.gemm over views into the stacked buffers."""
-        x = hidden_states
-        in_dtype = x.dtype
-        if in_dtype not in (torch.float16, torch.bfloat16):
-            x = x.to(torch.float16)
-        idx = top_k_index.long()
-        E, I, H = self.num_experts, self.intermediate_dim, self.hidden_dim
-        if bool(((idx < 0) | (idx >= E)).any()):
-            raise IndexError(f"HipMoeExperts: expert index out of range [0, {E})")
-        final = torch.zeros_like(x)
-        mask = torch.nn.functional.one_hot(idx, num_classes=E).permute(2, 1, 0)
-        for e in torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero().flatten().tolist():
-            pos, tok = torch.where(mask[e])
-            cur = x[tok].contiguous()
-            gu = ops.gemm(cur, self.gate_up_qweight[e], self.gate_up_meta[e], None, None, 2 * I, self.gate_up_group_size, self.bits,
-                          self.scale_dtype)
-            g, u = deinterleave_gate_up(gu)
-            h = (torch.nn.functional.silu(g) * u).contiguous()
-            d = ops.gemm(h, self.down_qweight[e], self.down_meta[e], None, None, H, self.down_group_size, self.bits, self.scale_dtype)
-            d = d * top_k_weights[tok, pos, None]
-            final.index_add_(0, tok, d.to(final.dtype))
-        return final if final.dtype == in_dtype else final.to(in_dtype)
+    def _expert_gemm(self, e: int, projection: str, x: torch.Tensor) -> torch.Tensor:
+        if projection == "gate_up":
+            return ops.gemm(x, self.gate_up_qweight[e], self.gate_up_meta[e], None, None, 2 * self.intermediate_dim, self.gate_up_group_size,
+                            self.bits, self.scale_dtype)
+        return ops.gemm(x, self.down_qweight[e], self.down_meta[e], None, None, self.hidden_dim, self.down_group_size, self.bits, self.scale_dtype)
 
 
 __all__ = ["HipMoeExperts", "MAX_FAST_TOKENS"]

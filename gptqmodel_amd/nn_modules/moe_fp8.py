@@ -17,25 +17,22 @@ Stacked layout (fixed by from_linears, on the device):
   down_weight uint8 [E, I * H], down_rscale fp32 [E, 1] | [E, H] | [E, H / br, I / bc]: the module's native layout, not interleaved.
 The reciprocals are the ones gptqhip_fp8_repack forms (IEEE fp32 division, once).
 
-* fast path (ops.moe_fp8_supported: H % 128 == 0, I % 128 == 0, T <= 16, top_k <= 16, fp16 | bf16): gptqhip_moe_fp8_gate_up + gptqhip_moe_fp8_down,
-  two launches into persistent buffers with the routing left on the device -- no host synchronisation, safe inside torch.cuda.graph.  An
-  expert id outside [0, E) contributes zero and sets a device status word, which check_status() reads (never forward()).
-  Rounding: stage one is the HF chain on HipFp8Linear's arithmetic (each projection rounded once, silu rounded, the product rounded); the
-  top_k expert outputs are combined in ONE fp32 weighted sum in slot order and rounded once.
+The call checks, the device-routed fast path, the status word and the host-routed slow path are StackedMoeExperts' (nn_modules/moe_base.py, which
+states the rounding contract); this module adds the FP8 stacking and:
+
+* fast path (ops.moe_fp8_supported: H % 128 == 0, I % 128 == 0, T <= 16, top_k <= 16, fp16 | bf16): gptqhip_moe_fp8_gate_up + gptqhip_moe_fp8_down.
 * slow path (more tokens, other dtypes): the host-routed per-expert loop of the HF module on ops.fp8_gemm over views into the same stacked
   buffers -- arithmetically what a loop over the original HipFp8Linear modules does.
 The expert-grouped path of HipMoeExperts has no FP8 counterpart."""
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..utils.model import deinterleave_gate_up
-
-MAX_FAST_TOKENS = 16
+from .moe_base import MAX_FAST_TOKENS, StackedMoeExperts
 
 
 def interleave_rows8(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
@@ -67,40 +64,23 @@ def _scale_rows(s: torch.Tensor, method: str, block: Optional[Tuple[int, int]], 
     return s.repeat_interleave(block[0], dim=0)
 
 
-def _is_hip_fp8(m) -> bool:
-    return bool(getattr(m, "_GPTQHIP_KERNEL_CLASS", False)) and getattr(m, "QUANT_TYPE", "") == "hip_fp8"
+class HipFp8MoeExperts(StackedMoeExperts):
+    _SOURCE_KIND = "HIP FP8 linear"
+    _RELEASE_NAMES = ("weight", "weight_scale_inv", "rscale")
 
-
-def _release(m) -> None:
-    """Drop a per-expert module's device tensors once they are stacked."""
-    for name in ("weight", "weight_scale_inv", "rscale"):
-        t = getattr(m, name, None)
-        if isinstance(t, torch.Tensor):
-            t.data = torch.empty(0, dtype=t.dtype, device=t.device)
-    m._ready = False
-
-
-class HipFp8MoeExperts(nn.Module):
     def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, gate_up_scale_method: str,
                  gate_up_block_size: Optional[Tuple[int, int]], down_scale_method: str, down_block_size: Optional[Tuple[int, int]]):
-        super().__init__()
-        self.num_experts = num_experts
-        self.hidden_dim = hidden_dim
-        self.intermediate_dim = intermediate_dim
+        super().__init__(num_experts, hidden_dim, intermediate_dim)
         self.fp8_format = "float8_e4m3fn"
         self.gate_up_scale_method = gate_up_scale_method      # of the source modules; the stacked scales are row or block (1, bc)
         self.gate_up_block_size = gate_up_block_size
         self.down_scale_method = down_scale_method
         self.down_block_size = down_block_size
         self.gate_up_block_cols = gate_up_block_size[1] if gate_up_scale_method == "block" else 0
-        self.training = False
-        self._scratch: Dict[Tuple, Tuple[torch.Tensor, ...]] = {}
-        self._fast_ok: Dict[Tuple[int, int], bool] = {}
 
-    def train(self, mode: bool = True):
-        if mode:      # the quantised linears it is built from refuse training mode the same way (SUPPORTS_TRAINING = False)
-            raise NotImplementedError("HipFp8MoeExperts: inference only (the HIP quant kernels have no backward)")
-        return super().train(False)
+    @staticmethod
+    def _is_source(m) -> bool:
+        return bool(getattr(m, "_GPTQHIP_KERNEL_CLASS", False)) and getattr(m, "QUANT_TYPE", "") == "hip_fp8"
 
     def _layout_repr(self, method, block) -> str:
         return f"block{tuple(block)}" if method == "block" else method
@@ -127,22 +107,14 @@ class HipFp8MoeExperts(nn.Module):
         fuse_gate_up_interleaved, all experts are stacked into two contiguous buffers per projection, and the per-expert copies are
         released as they are stacked (peak extra memory: one expert).  Down may carry a different scale layout from gate / up.  Raises
         NotImplementedError when the experts cannot share the stacked layout; nothing has been modified then."""
-        gate, up, down = list(gate), list(up), list(down)
-        E = len(gate)
-        if E == 0 or len(up) != E or len(down) != E:
-            raise NotImplementedError("from_linears needs three equal-length, non-empty lists")
-        g0, d0 = gate[0], down[0]
-        if not _is_hip_fp8(g0) or not _is_hip_fp8(d0):
+        gate, up, down = cls._check_lists(gate, up, down)
+        E, g0, d0 = len(gate), gate[0], down[0]
+        if not cls._is_source(g0) or not cls._is_source(d0):
             raise NotImplementedError(f"expert 0: {type(g0).__name__} / {type(d0).__name__} is not a HIP FP8 linear")
         H, I = g0.in_features, g0.out_features
         for e in range(E):
             for m, (k, n), ref in ((gate[e], (H, I), g0), (up[e], (H, I), g0), (down[e], (I, H), d0)):
-                if not _is_hip_fp8(m):
-                    raise NotImplementedError(f"expert {e}: {type(m).__name__} is not a HIP FP8 linear")
-                if getattr(m, "adapter", None) is not None or m.bias is not None:
-                    raise NotImplementedError(f"expert {e}: adapters / biases are not carried by the stacked experts")
-                if (m.in_features, m.out_features) != (k, n):
-                    raise NotImplementedError(f"expert {e}: shape {(m.in_features, m.out_features)} != {(k, n)}")
+                cls._check_module(e, m, k, n)
                 if m.fp8_format != "float8_e4m3fn" or (not m._ready and m.weight.dtype != torch.float8_e4m3fn):
                     raise NotImplementedError(f"expert {e}: {m.fp8_format} / {m.weight.dtype} weights (float8_e4m3fn only)")
                 if m.weight_scale_method != ref.weight_scale_method or m.weight_block_size != ref.weight_block_size:
@@ -185,7 +157,7 @@ class HipFp8MoeExperts(nn.Module):
                 bufs[2][e], bufs[3][e] = w_t, rs.reshape(-1)
                 del w_t, rs
             for m in (g, u, d):
-                _release(m)
+                cls._release(m)
         bufs[1] = bufs[1].view((E, 2 * I, H // gu_bc) if gu_bc else (E, 2 * I))
         bufs[3] = bufs[3].view((E,) + (tuple(d0._scale_shape()) or (1,)))
         for name, t in zip(("gate_up_weight", "gate_up_rscale", "down_weight", "down_rscale"), bufs):
@@ -218,76 +190,17 @@ class HipFp8MoeExperts(nn.Module):
             self._fast_ok[key] = ok
         return ok and dtype in (torch.float16, torch.bfloat16)
 
-    def _scratch_for(self, T: int, top_k: int, dtype: torch.dtype, device: torch.device):
-        key = (T, top_k, dtype)
-        s = self._scratch.get(key)
-        if s is None or s[0].device != device:
-            s = (torch.empty((T * top_k, self.intermediate_dim), dtype=dtype, device=device),
-                 torch.empty((T, self.hidden_dim), dtype=dtype, device=device),
-                 torch.empty((T, top_k), dtype=torch.int32, device=device),
-                 torch.empty((T, top_k), dtype=torch.float32, device=device))
-            self._scratch[key] = s
-        return s
-
-    def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
-        if hidden_states.dim() != 2 or hidden_states.shape[1] != self.hidden_dim or top_k_index.dim() != 2 \
-                or top_k_index.shape != top_k_weights.shape or top_k_index.shape[0] != hidden_states.shape[0]:
-            raise RuntimeError(f"HipFp8MoeExperts: expected hidden_states [T, {self.hidden_dim}] and top_k_index / top_k_weights [T, k], got "
-                               f"{tuple(hidden_states.shape)}, {tuple(top_k_index.shape)}, {tuple(top_k_weights.shape)}")
-        if not hidden_states.is_cuda:
-            raise RuntimeError("gptqmodel_amd HIP ops need tensors on a ROCm device (got a CPU tensor); there is no CPU fallback")
-        T, top_k = top_k_index.shape
-        if T == 0:
-            return torch.zeros_like(hidden_states)
-        if T > MAX_FAST_TOKENS or not self.fast_path(T, top_k, hidden_states.dtype):
-            return self._forward_loop(hidden_states, top_k_index, top_k_weights)
-        # the result lives in a persistent buffer of this module (one per (T, top_k, dtype)): the next call with that signature overwrites it
-        act, out, ids, w = self._scratch_for(T, top_k, hidden_states.dtype, hidden_states.device)
-        if top_k_index.dtype == torch.int32 and top_k_index.is_contiguous():
-            ids = top_k_index
-        else:
-            ids.copy_(top_k_index)
-        if top_k_weights.dtype == torch.float32 and top_k_weights.is_contiguous():
-            w = top_k_weights
-        else:
-            w.copy_(top_k_weights)
-        x = hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous()
+    def _fused_gate_up(self, x: torch.Tensor, ids: torch.Tensor, act: torch.Tensor) -> None:
         ops.moe_fp8_gate_up(x, self.gate_up_weight, self.gate_up_rscale, ids, act, self.status, self.num_experts, self.intermediate_dim,
                             self.gate_up_block_cols)
+
+    def _fused_down(self, act: torch.Tensor, ids: torch.Tensor, w: torch.Tensor, out: torch.Tensor) -> None:
         mode, block = self._down_mode()
         ops.moe_fp8_down(act, self.down_weight, self.down_rscale, ids, w, out, self.status, self.num_experts, mode, block)
-        return out
 
-    def check_status(self) -> None:
-        """Host read of the device status word (a synchronisation: call it outside the decode loop).  Raises IndexError when a fast-path call
-        since the last check met an expert id outside [0, num_experts) -- that slot contributed zero -- and clears the word."""
-        if int(self.status.item()) != 0:
-            self.status.zero_()
-            raise IndexError(f"HipFp8MoeExperts: expert index out of range [0, {self.num_experts}) in a fused MoE call")
-
-    def _forward_loop(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
-        """The experts loop of the HF module (host-routed) on ops.fp8_gemm over views into the stacked buffers."""
-        x = hidden_states
-        in_dtype = x.dtype
-        if in_dtype not in (torch.float16, torch.bfloat16):
-            x = x.to(torch.float16)
-        idx = top_k_index.long()
-        E = self.num_experts
-        if bool(((idx < 0) | (idx >= E)).any()):
-            raise IndexError(f"HipFp8MoeExperts: expert index out of range [0, {E})")
-        final = torch.zeros_like(x)
-        mask = torch.nn.functional.one_hot(idx, num_classes=E).permute(2, 1, 0)
-        for e in torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero().flatten().tolist():
-            pos, tok = torch.where(mask[e])
-            cur = x[tok].contiguous()
-            w, rs, mode, block, _, N = self.expert_view(e, "gate_up")
-            g, u = deinterleave_gate_up(ops.fp8_gemm(cur, w, rs, None, N, mode, block))
-            h = (torch.nn.functional.silu(g) * u).contiguous()
-            w, rs, mode, block, _, N = self.expert_view(e, "down")
-            d = ops.fp8_gemm(h, w, rs, None, N, mode, block)
-            d = d * top_k_weights[tok, pos, None]
-            final.index_add_(0, tok, d.to(final.dtype))
-        return final if final.dtype == in_dtype else final.to(in_dtype)
+    def _expert_gemm(self, e: int, projection: str, x: torch.Tensor) -> torch.Tensor:
+        w, rs, mode, block, _, N = self.expert_view(e, projection)
+        return ops.fp8_gemm(x, w, rs, None, N, mode, block)
 
 
 __all__ = ["HipFp8MoeExperts", "MAX_FAST_TOKENS", "interleave_rows8"]

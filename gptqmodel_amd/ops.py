@@ -267,15 +267,20 @@ def moe_supported(H: int, I: int, group_size: int, bits: int = 4, has_perm: bool
     return bool(_lib.load().gptqhip_moe_supported(H, I, group_size, bits, 1 if has_perm else 0, T, top_k))
 
 
-def _moe_check(what: str, x: torch.Tensor, rows: int, cols: int, ids: torch.Tensor, status: torch.Tensor, scale_dtype: torch.dtype):
-    if x.dtype not in _DT or scale_dtype not in _DT:
-        raise RuntimeError(f"{what}: unsupported dtypes x={x.dtype} scales={scale_dtype}")
+def _moe_io_check(what: str, x: torch.Tensor, rows: int, cols: int, ids: torch.Tensor, status: torch.Tensor):
+    """The x / ids / status checks of every few-token MoE stage, int4 and FP8."""
     if x.dim() != 2 or tuple(x.shape) != (rows, cols) or not x.is_contiguous():
         raise RuntimeError(f"{what}: input must be a contiguous [{rows}, {cols}] tensor (got {tuple(x.shape)})")
     if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
         raise RuntimeError(f"{what}: ids must be a contiguous int32 [T, top_k] tensor")
     if status.dtype != torch.int32 or status.numel() < 1:
         raise RuntimeError(f"{what}: status must be an int32 tensor")
+
+
+def _moe_check(what: str, x: torch.Tensor, rows: int, cols: int, ids: torch.Tensor, status: torch.Tensor, scale_dtype: torch.dtype):
+    if x.dtype not in _DT or scale_dtype not in _DT:
+        raise RuntimeError(f"{what}: unsupported dtypes x={x.dtype} scales={scale_dtype}")
+    _moe_io_check(what, x, rows, cols, ids, status)
 
 
 def moe_gate_up(x: torch.Tensor, qweight_t: torch.Tensor, meta: torch.Tensor, ids: torch.Tensor, act: torch.Tensor, status: torch.Tensor,
@@ -540,12 +545,7 @@ def _moe_fp8_check(what: str, x: torch.Tensor, rows: int, cols: int, ids: torch.
                    rscale: torch.Tensor, E: int, w_bytes: int, n_scales: int):
     if x.dtype not in _DT:
         raise RuntimeError(f"{what}: unsupported activation dtype {x.dtype}")
-    if x.dim() != 2 or tuple(x.shape) != (rows, cols) or not x.is_contiguous():
-        raise RuntimeError(f"{what}: input must be a contiguous [{rows}, {cols}] tensor (got {tuple(x.shape)})")
-    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
-        raise RuntimeError(f"{what}: ids must be a contiguous int32 [T, top_k] tensor")
-    if status.dtype != torch.int32 or status.numel() < 1:
-        raise RuntimeError(f"{what}: status must be an int32 tensor")
+    _moe_io_check(what, x, rows, cols, ids, status)
     if weight_t.dtype != torch.uint8 or weight_t.numel() != E * w_bytes or not weight_t.is_contiguous():
         raise RuntimeError(f"{what}: weight_t must be a contiguous uint8 tensor of E * {w_bytes} bytes")
     if rscale.dtype != torch.float32 or rscale.numel() != E * n_scales or not rscale.is_contiguous():

@@ -54,12 +54,13 @@ def fuse_moe_experts(block: nn.Module, grouped_routing: Optional[bool] = None) -
     tokens, which the FP8 stand-in does not have); None keeps its default (GPTQHIP_MOE_GROUPED=1 in the environment)."""
     try:
         from ..nn_modules.moe import HipMoeExperts
+        from ..nn_modules.moe_base import StackedMoeExperts
         from ..nn_modules.moe_fp8 import HipFp8MoeExperts
         mods = _expert_modules(block)
         if not mods:
             return _decline(block, "no container of per-expert modules under `experts`")
         experts = block.experts
-        if isinstance(experts, (HipMoeExperts, HipFp8MoeExperts)):
+        if isinstance(experts, StackedMoeExperts):
             return _decline(block, "already fused")
         if type(experts).forward is nn.Module.forward:
             return _decline(block, f"{type(experts).__name__} is indexed by the block's own forward: there is no "

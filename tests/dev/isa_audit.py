@@ -1,6 +1,6 @@
 """Dev tool: per-kernel register / scratch table of every translation unit (hipcc -Rpass-analysis=kernel-resource-usage; needs no
-GPU).  Usage: python tests/dev/isa_audit.py [out.txt]   -- prints one line per kernel instantiation: VGPRs, AGPRs, scratch bytes
-per lane, spilled VGPRs, occupancy, and a summary of the spilling ones."""
+GPU).  Usage: python tests/dev/isa_audit.py [out.txt]   -- prints one line per kernel instantiation: SGPRs, VGPRs, AGPRs, scratch bytes
+per lane, spilled VGPRs, LDS bytes per block, occupancy, and a summary of the spilling ones."""
 import os
 import re
 import subprocess
@@ -10,7 +10,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
 CSRC = os.path.join(ROOT, "gptqmodel_amd", "csrc")
-UNITS = ["gptqhip_skinny.hip", "gptqhip_tiled.hip", "gptqhip_tiled_f32.hip", "gptqhip_tiled8.hip", "gptqhip_aux.hip", "gptqhip_comm.hip"]
+UNITS = ["gptqhip_skinny.hip", "gptqhip_tiled.hip", "gptqhip_tiled_f32.hip", "gptqhip_tiled8.hip", "gptqhip_aux.hip", "gptqhip_comm.hip",
+         "gptqhip_moe.hip", "gptqhip_moe_grouped.hip", "gptqhip_fp8.hip", "gptqhip_moe_fp8.hip"]
 
 
 def audit(unit):
@@ -20,7 +21,7 @@ def audit(unit):
                            capture_output=True, text=True)
     rows, cur = [], None
     for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill): (\S+)", line)
+        m = re.search(r"remark:\s+(Function Name|TotalSGPRs|VGPRs|AGPRs|LDS Size \[bytes/block\]|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|VGPRs Spill|SGPRs Spill): (\S+)", line)
         if not m:
             continue
         k, v = m.group(1), m.group(2)
@@ -47,7 +48,9 @@ def main():
         for r in rows:
             sp = int(r.get("VGPRs Spill", 0))
             sc = int(r.get("ScratchSize [bytes/lane]", 0))
-            print(f"{r['demangled']:90s} vgpr {r.get('VGPRs'):>3s} agpr {r.get('AGPRs'):>3s} scratch {sc:4d} spill {sp:3d} occ {r.get('Occupancy [waves/SIMD]')}", file=out)
+            g = lambda k: r.get(k, "?")      # a compiler that omits a remark prints "?"  # noqa: E731
+            print(f"{r['demangled']:90s} sgpr {g('TotalSGPRs'):>3s} vgpr {g('VGPRs'):>3s} agpr {g('AGPRs'):>3s} scratch {sc:4d} spill {sp:3d} "
+                  f"lds {g('LDS Size [bytes/block]'):>5s} occ {g('Occupancy [waves/SIMD]')}", file=out)
             if sp or sc:
                 spill.append((unit, r["demangled"], sp, sc))
     print(f"## kernels with scratch / spills: {len(spill)}", file=out)
