@@ -28,26 +28,50 @@ LAYOUTS = {"tensor": (("tensor", None), ("tensor", None)), "row": (("row", None)
            "gu64x256_d32x128": (("block", (64, 256)), ("block", (32, 128)))}
 WIDE_LAYOUT_SHAPE = "1280x128e3k2"
 CASES = [(s, l) for s in sorted(SHAPES) for l in LAYOUTS if l != "gu64x256_d32x128" or s == WIDE_LAYOUT_SHAPE]
+# Deep shapes: the smallest at which a wave runs SEVERAL chunks of its contiguous range (tests/moe_wave_model.py derives, from the kernels'
+# constants, what each reaches) -- ranges longer than the look-ahead with a ragged last round, K blocks of 2 and 3 chunks that a wave boundary
+# cuts, top_k 7 / 8 / 16.  Seeds of their own (_seed0), so the inputs of the cases above keep their bits.
+DEEP_SHAPES = {"4224x128e3k2": (4224, 128, 3, 2), "128x4224e3k2": (128, 4224, 3, 2), "128x768e16k16": (128, 768, 16, 16),
+               "256x768e8k8": (256, 768, 8, 8), "256x384e7k7": (256, 384, 7, 7)}
+DEEP_LAYOUTS = {"gu64x384_d32x128": (("block", (64, 384)), ("block", (32, 128))), "gu128x128_d32x256": (("block", (128, 128)), ("block", (32, 256))),
+                "gu128x128_d32x384": (("block", (128, 128)), ("block", (32, 384)))}
+DEEP_CASES = [("4224x128e3k2", "row"), ("4224x128e3k2", "b128x128"), ("4224x128e3k2", "gu64x384_d32x128"),
+              ("128x4224e3k2", "tensor"), ("128x4224e3k2", "b128x128"), ("128x4224e3k2", "gu128x128_d32x384"),
+              ("128x768e16k16", "row"), ("128x768e16k16", "gu128x128_d32x256"), ("256x768e8k8", "tensor"), ("256x768e8k8", "gu128x128_d32x256"),
+              ("256x384e7k7", "row"), ("256x384e7k7", "b128x128")]
+DEEP_TOKENS = (1, 16)
+assert not set(DEEP_SHAPES) & set(SHAPES) and not set(DEEP_LAYOUTS) & set(LAYOUTS)
+_ALL_SHAPES = dict(SHAPES, **DEEP_SHAPES)
+_ALL_LAYOUTS = dict(LAYOUTS, **DEEP_LAYOUTS)
+_DEEP_SEED_BASE = 40                # first seed index of the deep shapes / layouts: past anything sorted(SHAPES) / sorted(LAYOUTS) can grow to
 PROJ = ("gate", "up", "down")
 
 
+def _shape_index(shape: str) -> int:
+    return _DEEP_SEED_BASE + sorted(DEEP_SHAPES).index(shape) if shape in DEEP_SHAPES else sorted(SHAPES).index(shape)
+
+
+def _layout_index(layout: str) -> int:
+    return _DEEP_SEED_BASE + sorted(DEEP_LAYOUTS).index(layout) if layout in DEEP_LAYOUTS else sorted(LAYOUTS).index(layout)
+
+
 def _seed0(shape: str, layout: str) -> int:
-    return 7000 + 977 * sorted(SHAPES).index(shape) + 101 * sorted(LAYOUTS).index(layout)
+    return 7000 + 977 * _shape_index(shape) + 101 * _layout_index(layout)
 
 
 def proj_dims(shape: str, name: str):
     """(N, K) of a projection's [N, K] weight."""
-    H, I = SHAPES[shape][:2]
+    H, I = _ALL_SHAPES[shape][:2]
     return (H, I) if name == "down" else (I, H)
 
 
 def proj_layout(layout: str, name: str):
-    return LAYOUTS[layout][1 if name == "down" else 0]
+    return _ALL_LAYOUTS[layout][1 if name == "down" else 0]
 
 
 def make_experts(shape: str, layout: str, lo: float = 200.0, hi: float = 6.0e4):
     """-> list of E dicts {gate, up, down}, each (codes uint8 [N, K], scale_inv float32 in the projection's layout)."""
-    E = SHAPES[shape][2]
+    E = _ALL_SHAPES[shape][2]
     seed0 = _seed0(shape, layout) + (0 if hi <= 6.0e4 else 50000)
     out = []
     for e in range(E):
@@ -123,8 +147,8 @@ def evaluate(experts, w64, layout: str, x, ids, rw, act: str, with_chain: bool =
 @functools.lru_cache(maxsize=None)
 def case(shape: str, layout: str, T: int, act: str):
     """The inputs and oracle outputs of one GPU test case, computed once per process and left unchanged."""
-    H, I, E, k = SHAPES[shape]
-    seed = 100 * sorted(SHAPES).index(shape) + T
+    H, I, E, k = _ALL_SHAPES[shape]
+    seed = 100 * _shape_index(shape) + T
     x = MO.make_x(8000 + seed, T, H, act).astype(np.float64)
     ids, rw = MO.make_routing(9000 + seed, T, E, k, act)
     out = evaluate(experts_of(shape, layout), weights64_of(shape, layout), layout, x, ids, rw, act)
@@ -142,7 +166,7 @@ def bar(c) -> float:
 def model_down_f32(shape: str, layout: str, c, act: str, reverse: bool = True) -> np.ndarray:
     """act_model -> down as an implementation of the stage-two contract may compute it: the kernels' fp32 weights (code * fp32 reciprocal),
     fp32 accumulation chunk by chunk (in reversed chunk order), ONE fp32 weighted sum in slot order, ONE rounding."""
-    H, I, E, k = SHAPES[shape]
+    H, I, E, k = _ALL_SHAPES[shape]
     block = proj_layout(layout, "down")[1]
     kw = [F.kernel_w(*ex["down"], block) for ex in experts_of(shape, layout)]
     ids, rw, a = c["ids"], c["rw"], c["act_model"].astype(np.float32)

@@ -21,13 +21,29 @@ from oracle import gptq_oracle as O
 SHAPES = {"256x128e8k2": (256, 128, 8, 2, 128), "384x640e5k3": (384, 640, 5, 3, 128), "512x256e4k4gK": (512, 256, 4, 4, -1)}
 TOKENS = (1, 2, 5, 16)
 GS64_SHAPE = "256x128e4k2g64"      # group_size 64: outside the fused ops, served by the module's host-routed loop
-_ALL_SHAPES = dict(SHAPES, **{GS64_SHAPE: (256, 128, 4, 2, 64)})
+_SEEDED_SHAPES = dict(SHAPES, **{GS64_SHAPE: (256, 128, 4, 2, 64)})      # (their sorted order fixes the seeds of every case above: add nothing here)
+# Deep shapes: the smallest at which a wave of the MoE kernels runs SEVERAL 128-row chunks (tests/moe_wave_model.py derives, from the kernels'
+# constants, what each reaches) -- more chunks than the look-ahead with a ragged last round, chunks of one wave in different groups
+# (group_size 256), top_k 7 / 8 / 16, and H wide enough for several column blocks of the grouped path's combine.  Seeds of their own
+# (_seed_index), so the inputs of the shapes above keep their bits.
+DEEP_SHAPES = {"4224x128e3k2": (4224, 128, 3, 2, 128), "128x4224e3k2": (128, 4224, 3, 2, 128), "2304x1536e4k4g256": (2304, 1536, 4, 4, 256),
+               "256x1408e8k8": (256, 1408, 8, 8, 128), "128x640e16k16": (128, 640, 16, 16, 128), "256x384e7k7": (256, 384, 7, 7, 128)}
+DEEP_TOKENS = (1, 16)
+assert not set(DEEP_SHAPES) & set(_SEEDED_SHAPES)
+_ALL_SHAPES = dict(_SEEDED_SHAPES, **DEEP_SHAPES)
+_DEEP_SEED_BASE = 40                # first seed index of the deep shapes: past anything sorted(_SEEDED_SHAPES) can grow to
+
+
+def _seed_index(shape: str) -> int:
+    if shape in DEEP_SHAPES:
+        return _DEEP_SEED_BASE + sorted(DEEP_SHAPES).index(shape)
+    return sorted(_SEEDED_SHAPES).index(shape)
 
 
 def make_experts(shape: str, scale_dtype: str):
     """-> list of E dicts {gate, up, down}, each (qweight, qzeros, scales, g_idx) as synth_gptq makes them (scales in [0.005, 0.015])."""
     H, I, E, _, gs = _ALL_SHAPES[shape]
-    seed0 = 3000 + 17 * sorted(_ALL_SHAPES).index(shape)
+    seed0 = 3000 + 17 * _seed_index(shape)
     out = []
     for e in range(E):
         out.append({"gate": synth_gptq(seed0 + 3 * e, 4, H, I, H if gs < 0 else gs, scale_dtype=scale_dtype),
@@ -97,7 +113,7 @@ def evaluate(weights, x, ids, rw, act):
 def case(shape: str, T: int, act: str, scale_dtype: str):
     """The inputs and oracle outputs of one GPU test case, computed once per process and left unchanged."""
     H, I, E, k, _ = _ALL_SHAPES[shape]
-    seed = 100 * sorted(_ALL_SHAPES).index(shape) + T
+    seed = 100 * _seed_index(shape) + T
     x = make_x(5000 + seed, T, H, act)
     ids, rw = make_routing(6000 + seed, T, E, k, act)
     out = evaluate(rounded_weights(shape, act, scale_dtype), x, ids, rw, act)

@@ -100,6 +100,52 @@ def test_stages_and_module_against_the_oracle(shape, T, act, scale_dtype):
 
 
 @pytest.mark.parametrize("act,scale_dtype", WEIGHT_RANGE_DTYPES)
+@pytest.mark.parametrize("T", MO.DEEP_TOKENS)
+@pytest.mark.parametrize("shape", sorted(MO.DEEP_SHAPES))
+def test_deep_k_and_wide_top_k_against_the_oracle(shape, T, act, scale_dtype):
+    """Waves that run several chunks (rounds of kMoeAhead loads with a ragged last one, chunks of one wave in different groups) and top_k 7, 8
+    and 16 -- what each shape reaches: tests/test_moe_wave_model_cpu.py.  The assertions and bars of test_stages_and_module_against_the_oracle."""
+    from gptqmodel_amd import ops
+    c = MO.case(shape, T, act, scale_dtype)
+    m = fused_experts(shape, scale_dtype)
+    assert m.fast_path(T, c["ids"].shape[1], TDT[act])
+    x, ids, rw = dev(c["x"], act), dev(c["ids"]), dev(c["rw"])
+    a, y, st = run_ops(m, x, ids, rw, act)
+    e1 = rel_err(torch_to_f32(a), c["act_ref"])
+    y2 = torch.empty_like(y)
+    st2 = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ops.moe_down(dev(c["act_ref"], act), m.down_qweight, m.down_meta, ids, rw, y2, st2, m.num_experts, m.down_group_size, m.scale_dtype)
+    e2 = MO.rel64(torch_to_f32(y2), c["y64"])
+    e3 = MO.rel64(torch_to_f32(y), c["y64"])
+    ym = m(x, ids.long(), rw.to(TDT[act]))
+    e4 = MO.rel64(torch_to_f32(ym), c["y64"])
+    print(f"deep {shape} T={T} {act}x{scale_dtype}: stage1 {e1:.3e} (bar {NORM_TOL[act]:.0e}); stage2 {e2:.3e}, both {e3:.3e}, module {e4:.3e} "
+          f"(bar {bar(c):.3e}: chain {MO.rel64(c['chain'], c['y64']):.3e}, one rounding {MO.rel64(c['y_once'], c['y64']):.3e})")
+    assert st == 0 and int(st2.item()) == 0
+    m.check_status()
+    assert e1 <= NORM_TOL[act], e1
+    assert e2 <= bar(c), (e2, bar(c))
+    assert e3 <= bar(c), (e3, bar(c))
+    assert e4 <= bar(c), (e4, bar(c))
+    assert torch.equal(ym, y)
+
+
+@pytest.mark.parametrize("act,scale_dtype", WEIGHT_RANGE_DTYPES)
+@pytest.mark.parametrize("shape", ["2304x1536e4k4g256", "256x1408e8k8"])
+def test_a_tokens_bits_do_not_depend_on_its_batch_or_the_run(shape, act, scale_dtype):
+    c = MO.case(shape, 16, act, scale_dtype)
+    m = fused_experts(shape, scale_dtype)
+    x, ids, rw = dev(c["x"], act), dev(c["ids"]), dev(c["rw"])
+    a, y, _ = run_ops(m, x, ids, rw, act)
+    a_b, y_b, _ = run_ops(m, x, ids, rw, act)
+    assert torch.equal(a, a_b) and torch.equal(y, y_b)               # two runs: the same bits
+    k = ids.shape[1]
+    for t in (0, 7, 15):                                             # a token alone: the bits it has inside the batch of 16
+        a1, y1, _ = run_ops(m, x[t:t + 1].contiguous(), ids[t:t + 1].contiguous(), rw[t:t + 1].contiguous(), act)
+        assert torch.equal(a1, a[t * k:(t + 1) * k]) and torch.equal(y1, y[t:t + 1]), t
+
+
+@pytest.mark.parametrize("act,scale_dtype", WEIGHT_RANGE_DTYPES)
 def test_routing_corners(act, scale_dtype):
     shape = "384x640e5k3"
     H, I, E, k, _ = MO.SHAPES[shape]

@@ -108,12 +108,42 @@ def test_stages_and_module_against_the_oracle(shape, layout, T, act):
     assert torch.equal(ym, y)
 
 
-@pytest.mark.parametrize("shape,layout", MF.CASES)
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("T", MF.DEEP_TOKENS)
+@pytest.mark.parametrize("shape,layout", MF.DEEP_CASES)
+def test_deep_k_and_wide_top_k_against_the_oracle(shape, layout, T, act):
+    """Waves whose contiguous range is several chunks long (rounds of kMoeAhead loads with a ragged last one, K blocks of 2 and 3 chunks that a
+    wave boundary cuts) and top_k 7, 8 and 16 -- what each case reaches: tests/test_moe_wave_model_cpu.py.  The assertions and bars of
+    test_stages_and_module_against_the_oracle."""
+    c = MF.case(shape, layout, T, act)
+    m = fused_experts(shape, layout)
+    assert m.fast_path(T, c["ids"].shape[1], TDT[act])
+    x, ids, rw = dev(c["x"], act), dev(c["ids"]), dev(c["rw"])
+    a, y, st = run_ops(m, x, ids, rw)
+    e1 = rel_err(host(a), c["act_model"])
+    y2, st2 = stage_two(m, dev(c["act_model"], act), ids, rw)
+    e2 = F.rel64(host(y2), c["y64"])
+    e3 = F.rel64(host(y), c["y64"])
+    ym = m(x, ids.long(), rw.to(TDT[act]))
+    e4 = F.rel64(host(ym), c["y64"])
+    b = MF.bar(c)
+    print(f"deep {shape} {layout} T={T} {act}: stage1 {e1:.3e} (bar {NORM_TOL[act]:.0e}); stage2 {e2:.3e}, both {e3:.3e}, module {e4:.3e} "
+          f"(bar {b:.3e}: chain {F.rel64(c['chain'], c['y64']):.3e}, one rounding {F.rel64(c['y_once'], c['y64']):.3e})")
+    assert st == 0 and int(st2.item()) == 0
+    m.check_status()
+    assert e1 <= NORM_TOL[act], e1
+    assert e2 <= b, (e2, b)
+    assert e3 <= b, (e3, b)
+    assert e4 <= b, (e4, b)
+    assert torch.equal(ym, y)
+
+
+@pytest.mark.parametrize("shape,layout", MF.CASES + MF.DEEP_CASES)
 def test_stacked_layout_is_the_interleaved_kernel_weights(shape, layout):
     """Independent of the MoE kernels: gptqhip_fp8_dequant on expert e's view of each stacked buffer = the oracle's kernel weights, bit for bit."""
     from gptqmodel_amd import ops
     m = fused_experts(shape, layout)
-    H, I, E, _ = MF.SHAPES[shape]
+    H, I, E, _ = MF._ALL_SHAPES[shape]
     ex = MF.experts_of(shape, layout)
     gu_block, d_block = MF.proj_layout(layout, "gate")[1], MF.proj_layout(layout, "down")[1]
     assert tuple(m.gate_up_weight.shape) == (E, 2 * I * H) and tuple(m.down_weight.shape) == (E, I * H)
@@ -201,7 +231,8 @@ def test_out_of_range_ids_set_status_and_contribute_zero(layout):
 
 
 @pytest.mark.parametrize("act", ACTS)
-@pytest.mark.parametrize("shape,layout", [("384x640e5k3", "b128x128"), ("256x256e8k8", "row"), ("1280x128e3k2", "gu64x256_d32x128")])
+@pytest.mark.parametrize("shape,layout", [("384x640e5k3", "b128x128"), ("256x256e8k8", "row"), ("1280x128e3k2", "gu64x256_d32x128"),
+                                          ("4224x128e3k2", "gu64x384_d32x128"), ("256x768e8k8", "gu128x128_d32x256")])
 def test_a_tokens_bits_do_not_depend_on_its_batch(shape, layout, act):
     c = MF.case(shape, layout, 16, act)
     m = fused_experts(shape, layout)

@@ -103,6 +103,46 @@ def test_stages_against_the_oracle(shape, T, act, scale_dtype):
 
 
 @pytest.mark.parametrize("act,scale_dtype", WEIGHT_RANGE_DTYPES)
+@pytest.mark.parametrize("T", (5, 33))
+@pytest.mark.parametrize("shape", ["4224x128e3k2", "128x4224e3k2", "2304x1536e4k4g256"])
+def test_deep_k_stages_against_the_oracle(shape, T, act, scale_dtype):
+    """Waves that run several chunks (rounds of kGroupedAhead loads with a ragged last one, chunks of one wave in different groups) and a combine
+    of 3 and 5 column blocks whose last is partial (part is NaN-poisoned by run_grouped) -- what each shape reaches:
+    tests/test_moe_wave_model_cpu.py.  The assertions and bars of test_stages_against_the_oracle."""
+    c = MO.case(shape, T, act, scale_dtype)
+    m = fused_experts(shape, scale_dtype)
+    assert m.grouped_path(T, c["ids"].shape[1], TDT[act])
+    x, ids, rw = dev(c["x"], act), dev(c["ids"]), dev(c["rw"])
+    a, y, st = run_grouped(m, x, ids, rw, act)
+    e1 = rel_err(torch_to_f32(a), c["act_ref"])
+    _, y2, st2 = run_grouped(m, x, ids, rw, act, act_in=dev(c["act_ref"], act))
+    e2, e3 = MO.rel64(torch_to_f32(y2), c["y64"]), MO.rel64(torch_to_f32(y), c["y64"])
+    print(f"deep {shape} T={T} {act}x{scale_dtype}: stage1 {e1:.3e} (bar {NORM_TOL[act]:.0e}); stage2 {e2:.3e}, pipeline {e3:.3e} (bar {bar(c):.3e})")
+    assert st == 0 and st2 == 0
+    assert e1 <= NORM_TOL[act], e1
+    assert e2 <= bar(c), (e2, bar(c))
+    assert e3 <= bar(c), (e3, bar(c))
+    if T <= 16:      # the ungrouped ops serve this too: both inside the bar
+        _, yu, stu = run_ops(m, x, ids, rw, act)
+        eu = MO.rel64(torch_to_f32(yu), c["y64"])
+        print(f"deep {shape} T={T} {act}x{scale_dtype}: ungrouped ops {eu:.3e}")
+        assert stu == 0 and eu <= bar(c)
+
+
+def test_deep_k_module_grouped_path_equals_the_four_ops():
+    shape, act, sdt, T = "2304x1536e4k4g256", "fp16", "fp16", 33
+    c = MO.case(shape, T, act, sdt)
+    m = grouped_experts(shape, sdt)
+    x, ids, rw = dev(c["x"], act), dev(c["ids"]), dev(c["rw"])
+    _, want, _ = run_grouped(m, x, ids, rw, act)
+    got = m(x, ids.long(), rw.to(TDT[act]))
+    assert torch.equal(got, want)
+    assert MO.rel64(torch_to_f32(got), c["y64"]) <= bar(c)
+    m.check_status()
+    assert len(m._grouped_eager) == 1
+
+
+@pytest.mark.parametrize("act,scale_dtype", WEIGHT_RANGE_DTYPES)
 def test_batch_independence(act, scale_dtype):
     shape, T = "384x640e5k3", 70
     c = MO.case(shape, T, act, scale_dtype)

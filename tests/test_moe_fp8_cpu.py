@@ -2,6 +2,7 @@
 the interleave rule, the C ABI's predicate and argument validation, and what fuse_moe_experts / from_linears decline.  Nothing here launches a
 kernel."""
 import ctypes
+import zlib
 
 import numpy as np
 import pytest
@@ -90,6 +91,55 @@ def test_the_model_of_the_contract_fits_its_own_bars(shape, layout, act):
         e = F.rel64(MF.model_down_f32(shape, layout, c, act), c["y64"])
         assert e <= MF.bar(c), (T, e, MF.bar(c))
         assert F.rel64(c["y_once"], c["y64"]) <= F.rel64(c["chain"], c["y64"]) + 1e-4      # one rounding is never the worse of the two
+
+
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("shape,layout", MF.DEEP_CASES)
+def test_the_model_of_the_contract_fits_its_own_bars_on_the_deep_cases(shape, layout, act):
+    """The conditions of test_the_model_of_the_contract_fits_its_own_bars on every case of test_deep_k_and_wide_top_k_against_the_oracle."""
+    for T in MF.DEEP_TOKENS:
+        c = MF.case(shape, layout, T, act)
+        assert all(np.isfinite(c[k]).all() for k in ("act_model", "y64", "y_once", "chain"))
+        e = F.rel64(MF.model_down_f32(shape, layout, c, act), c["y64"])
+        print(f"{shape} {layout} T={T} {act}: model {e:.3e} (bar {MF.bar(c):.3e}: chain {F.rel64(c['chain'], c['y64']):.3e}, "
+              f"one rounding {F.rel64(c['y_once'], c['y64']):.3e}) max|act_model|={float(np.abs(c['act_model']).max()):.3g}")
+        assert e <= MF.bar(c), (T, e, MF.bar(c))
+        assert F.rel64(c["y_once"], c["y64"]) <= F.rel64(c["chain"], c["y64"]) + 1e-4
+
+
+def test_deep_cases_are_apart_from_the_existing_ones():
+    assert len(MF.CASES) == 13 and len(MF.DEEP_CASES) == 12 and not set(MF.DEEP_CASES) & set(MF.CASES)
+    assert {s for s, _ in MF.DEEP_CASES} == set(MF.DEEP_SHAPES) and set(MF.DEEP_LAYOUTS) <= {l for _, l in MF.DEEP_CASES}
+    for shape, layout in MF.DEEP_CASES:      # every block divides its projection
+        for name in MF.PROJ:
+            (N, K), (method, block) = MF.proj_dims(shape, name), MF.proj_layout(layout, name)
+            assert block is None or (N % block[0] == 0 and K % block[1] == 0), (shape, layout, name)
+    old = {MF._seed0(s, l) for s, l in MF.CASES}
+    new = {MF._seed0(s, l) for s, l in MF.DEEP_CASES}
+    assert len(new) == 12 and min(new) > max(old) + 6 * 16
+
+
+def crc(a) -> int:
+    return zlib.crc32(np.ascontiguousarray(a).tobytes())
+
+
+# (shape, layout, T, act) -> crc32 of x, ids, rw, expert 0's gate codes, the last expert's down scale_inv and chain, recorded on the commit before
+# DEEP_SHAPES / DEEP_LAYOUTS existed: adding them must not move the seeds, and with them the inputs, of any case that was there before
+PINNED_INPUTS = {
+    ("1280x128e3k2", "gu64x256_d32x128", 5, "fp16"): (3169201390, 3732383910, 556380046, 4281994224, 3155888974, 325525882),
+    ("256x256e8k8", "row", 16, "bf16"): (93289943, 3617835931, 979495653, 346879391, 1686543588, 3152011844),
+    ("384x640e5k3", "b128x128", 2, "fp16"): (1750784163, 1499497953, 2054021073, 2023461098, 3013506786, 2373060410),
+    ("256x128e8k2", "tensor", 1, "bf16"): (2579204185, 4091379325, 2815860233, 394158350, 1378013163, 3359235249),
+}
+
+
+@pytest.mark.parametrize("key", sorted(PINNED_INPUTS))
+def test_inputs_of_the_existing_cases_keep_their_bits(key):
+    shape, layout, T, act = key
+    c, ex = MF.case(*key), MF.experts_of(shape, layout)
+    assert c["x"].dtype == np.float64 and c["ids"].dtype == np.int32 and ex[0]["gate"][0].dtype == np.uint8
+    got = (crc(c["x"]), crc(c["ids"]), crc(c["rw"]), crc(ex[0]["gate"][0]), crc(ex[-1]["down"][1]), crc(c["chain"]))
+    assert got == PINNED_INPUTS[key], got
 
 
 # ---- layout ------------------------------------------------------------------------------------------------------------------------------

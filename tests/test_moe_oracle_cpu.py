@@ -3,6 +3,7 @@ of the gptqhip_moe_* entry points answer without touching a device, and the bar 
 its own inputs (one rounding of the float64 result is never further from it than the reference chain is)."""
 import ctypes
 import os
+import zlib
 
 import numpy as np
 import pytest
@@ -96,3 +97,46 @@ def test_bar_in_force_on_the_gpu_test_inputs(shape, T, act, scale_dtype):
     print(f"{shape} T={T} {act}x{scale_dtype}: rel_err(chain, y64)={e_chain:.3e} rel_err(y64 rounded once, y64)={e_once:.3e}")
     assert e_once <= e_chain, (e_once, e_chain)
     assert np.isfinite(c["chain"]).all() and float(np.abs(c["y64"]).max()) > 1e-3
+
+
+@pytest.mark.parametrize("act,scale_dtype", WEIGHT_RANGE_DTYPES)
+@pytest.mark.parametrize("T", MO.DEEP_TOKENS)
+@pytest.mark.parametrize("shape", sorted(MO.DEEP_SHAPES))
+def test_bar_in_force_on_the_deep_gpu_test_inputs(shape, T, act, scale_dtype):
+    """The condition of test_bar_in_force_on_the_gpu_test_inputs on every case of test_deep_k_and_wide_top_k_against_the_oracle."""
+    c = MO.case(shape, T, act, scale_dtype)
+    e_chain, e_once = MO.rel64(c["chain"], c["y64"]), MO.rel64(c["y_once"], c["y64"])
+    print(f"{shape} T={T} {act}x{scale_dtype}: rel_err(chain, y64)={e_chain:.3e} rel_err(y64 rounded once, y64)={e_once:.3e} "
+          f"max|act_ref|={float(np.abs(c['act_ref']).max()):.3g}")
+    assert e_once <= e_chain, (e_once, e_chain)
+    assert np.isfinite(c["chain"]).all() and np.isfinite(c["act_ref"]).all() and float(np.abs(c["y64"]).max()) > 1e-3
+
+
+def crc(a) -> int:
+    return zlib.crc32(np.ascontiguousarray(a).tobytes())
+
+
+# (shape, T, act, scale_dtype) -> crc32 of x, ids, rw, expert 0's gate qweight, the last expert's down scales and chain, recorded on the commit
+# before DEEP_SHAPES existed: adding shapes must not move the seeds, and with them the inputs, of any case that was there before
+PINNED_INPUTS = {
+    ("384x640e5k3", 5, "fp16", "fp16"): (3309585142, 835754259, 631227568, 2735770339, 2432401560, 1693009199),
+    ("512x256e4k4gK", 16, "bf16", "bf16"): (2907791435, 1350817424, 2812721836, 4073838750, 358299668, 696317412),
+    ("256x128e8k2", 1, "fp16", "bf16"): (730660419, 3602260385, 609785316, 1835270922, 2075872091, 1310518014),
+    (MO.GS64_SHAPE, 17, "fp16", "fp16"): (3514689607, 3191745950, 2445480233, 2770426853, 676093602, 1817073913),
+}
+
+
+@pytest.mark.parametrize("key", sorted(PINNED_INPUTS))
+def test_inputs_of_the_existing_cases_keep_their_bits(key):
+    shape, T, act, scale_dtype = key
+    c, ex = MO.case(*key), MO.experts_of(shape, scale_dtype)
+    assert c["x"].dtype == np.float32 and c["ids"].dtype == np.int32 and ex[0]["gate"][0].dtype == np.int32
+    got = (crc(c["x"]), crc(c["ids"]), crc(c["rw"]), crc(ex[0]["gate"][0]), crc(ex[-1]["down"][2]), crc(c["chain"]))
+    assert got == PINNED_INPUTS[key], got
+
+
+def test_deep_shapes_have_seeds_of_their_own():
+    assert not set(MO.DEEP_SHAPES) & set(MO.SHAPES) and MO.GS64_SHAPE not in MO.DEEP_SHAPES
+    old = {MO._seed_index(s) for s in MO._SEEDED_SHAPES}
+    new = {MO._seed_index(s) for s in MO.DEEP_SHAPES}
+    assert old == set(range(len(MO._SEEDED_SHAPES))) and len(new) == len(MO.DEEP_SHAPES) and min(new) > max(old)
