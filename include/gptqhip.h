@@ -393,7 +393,8 @@ int gptqhip_gather_cols(const void* x, const int32_t* perm, void* out, int M, in
  * rounded once).  The callers of the q|k|v and gate|up QuantLinears are RMSNorms; their siblings share one g_idx, so the
  * normalised x can leave the norm kernel already in the kernel's row order and gptqhip_gemm runs with perm = NULL -- the separate
  * x gather per linear (ExllamaV2 does it while staging A: gptqmodel_ext/exllamav2/cuda/q_gemm_kernel_gptq.cuh:79-90) disappears.
- * h, out [M,K] act dtype (out must not alias h), weight [K] act dtype, K % 8 == 0, K <= 16384. */
+ * h, out [M,K] act dtype (out must not alias h), weight [K] act dtype, K % 8 == 0, K <= 16384.  The fp32 SUM of a row's squares, not just
+ * their mean, must stay finite: a bf16 row whose sum exceeds FLT_MAX is normalised with 1 / rms = 0 (HF's fp32 mean overflows the same way). */
 int gptqhip_rmsnorm_gather(const void* h, const void* weight, const int32_t* perm, void* out, int M, int K, float eps, int act_dtype,
                            gptqhip_stream_t stream);
 

@@ -188,6 +188,8 @@ def test_comm_buffer_sizes_and_collective_argument_checks(lib):
     assert lib.gptqhip_rmsnorm_gather(one, one, None, one, 4, 4096, 1e-5, 0, None) == -22                          # out aliases h
     assert lib.gptqhip_rmsnorm_gather(one, ctypes.c_void_p(512), None, ctypes.c_void_p(1024), 4, 4100, 1e-5, 0, None) == -22
     assert lib.gptqhip_rmsnorm_gather(one, one, None, one, 0, 4096, 1e-5, 0, None) == 0                            # empty batch
+    assert lib.gptqhip_rmsnorm_gather(one, ctypes.c_void_p(512), None, ctypes.c_void_p(1024), 4, 16392, 1e-5, 0, None) == -22   # K > 16384: a staged row would not fit
+    assert lib.gptqhip_gather_cols(one, one, ctypes.c_void_p(1024), 0, 4096, None) == 0                                # empty batch
 
 
 def test_argument_validation_reports_errors_without_a_gpu(lib):
