@@ -67,6 +67,9 @@ SIGNATURES = {
     "gptqhip_moe_fp8_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "gptqhip_moe_fp8_gate_up": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_moe_fp8_down": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gptqhip_moe_fp8_grouped_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "gptqhip_moe_fp8_gate_up_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gptqhip_moe_fp8_down_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_pack_gptq": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_pack_gptq_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "gptqhip_gather_cols": (_i, [_vp, _vp, _vp, _i, _i, _vp]),

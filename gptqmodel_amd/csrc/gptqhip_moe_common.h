@@ -1,5 +1,6 @@
-// What the device-routed MoE translation units share (gptqhip_moe.hip, gptqhip_moe_fp8.hip, gptqhip_moe_grouped.hip): the constants of the
-// few-token kernels, the masked-K-step fragments, and the two NUMERICS CONTRACTS of the experts path, each stated and written ONCE here:
+// What the device-routed MoE translation units share (gptqhip_moe.hip, gptqhip_moe_fp8.hip, gptqhip_moe_grouped.hip, gptqhip_moe_fp8_grouped.hip):
+// the constants of the few-token kernels, the limits and unit size of the expert-grouped path, the masked-K-step fragments, and the two NUMERICS
+// CONTRACTS of the experts path, each stated and written ONCE here:
 //
 //   SiLU * up   (moe_silu_up)         y = act(v) for the gate and the up column, s = act(silu(y_gate)) with the accurate expf, a = act(s * y_up):
 //                                     the rounding chain of GPTQHIP_OUT_SILU_MUL_PAIRED = HF's act_fn(gate) * up in the activation dtype.
@@ -10,8 +11,9 @@
 //                                     rounds every expert's output and every product and accumulates in the activation dtype through index_add_); it
 //                                     is the choice the tensor-parallel path made.  moe_combine_kernel (grouped path) restates it on 4-wide vectors.
 //
-// NOT shared, on purpose: the three inner loops.  The int4 few-token loop deals chunks to waves strided (w, w + W, ..), the FP8 loop deals contiguous
-// ranges and flushes at K-block boundaries, the grouped loop carries 16 real rows: each fixes a summation order and with it the output bits.
+// NOT shared, on purpose: the inner loops.  The int4 few-token loop deals chunks to waves strided (w, w + W, ..), the FP8 loop deals contiguous
+// ranges and flushes at K-block boundaries, the grouped loops (int4 strided, FP8 contiguous) carry 16 real rows: each fixes a summation order and
+// with it the output bits.
 //
 // Host side: the argument checks every entry point runs, in the order they are listed here; the entry point's name leads every message.
 #pragma once
@@ -27,6 +29,18 @@ constexpr int kMoeMaxRows = 16;      // few-token ops: tokens per call, and slot
 constexpr int kMoeGateUpWaves = 8;   // most waves of a gate_up block (in-block split-K)
 constexpr int kMoeDownWaves = 16;    // most waves of a down block
 constexpr int kMoeAhead = 4;         // chunks whose loads a wave issues before consuming the first
+
+// expert-grouped path (gptqhip_moe_grouped.hip: align, int4 stages, combine; gptqhip_moe_fp8_grouped.hip: FP8 stages)
+constexpr int kGroupedMaxExperts = 512;    // cnt[16][E] ints of LDS: 32 KiB at E = 512
+constexpr int kGroupedMaxSlots = 65536;    // max_units <= 4576 blocks in grid.y
+constexpr int kGroupedMaxTopK = 16;
+constexpr int kUnitRows = 16;
+
+__host__ __device__ inline int grouped_units(int S, int E) {
+    const int ne = S < E ? S : E;
+    const int u = (S + 15 * ne) / 16;
+    return u < S ? u : S;
+}
 
 // ---- device ----------------------------------------------------------------------------------------------------------------------------------
 // Masked K-steps: lane (rq, c) loads the 8 activations of K-step c & 3 (rows 8 rq .. 8 rq + 7 of it), so MFMA row m carries K-step m & 3.  K-step j
@@ -162,6 +176,60 @@ inline void moe_dispatch(int act_dtype, int scale_dtype, Launch&& launch) {
     if (act_dtype == GPTQHIP_FP16 && scale_dtype == GPTQHIP_FP16) launch(fp16{}, fp16{});
     else if (act_dtype == GPTQHIP_BF16) launch(bf16{}, bf16{});
     else launch(fp16{}, bf16{});
+}
+
+// ---- expert-grouped path: routing limits and pointer lists ------------------------------------------------------------------------------------
+inline bool grouped_routing_ok(int T, int top_k, int E) {
+    return T >= 1 && top_k >= 1 && top_k <= kGroupedMaxTopK && E >= 1 && E <= kGroupedMaxExperts && (long long)T * top_k <= kGroupedMaxSlots;
+}
+
+inline int grouped_check_ptrs(const char* fn, const void* const* ptrs16, int n16, const void* const* ptrs4, int n4) {
+    return moe_check_ptrs(fn, ptrs16, n16, "activations, weights, constants, partial sums and outputs", ptrs4, n4,
+                          "ids, weights, sort buffers and status");
+}
+
+inline int grouped_check_routing(const char* fn, int T, int top_k, int E) {
+    if (!grouped_routing_ok(T, top_k, E)) {
+        set_error("%s: T=%d top_k=%d E=%d outside T >= 1, 1 <= top_k <= %d, 1 <= E <= %d, T * top_k <= %d", fn, T, top_k, E, kGroupedMaxTopK,
+                  kGroupedMaxExperts, kGroupedMaxSlots);
+        return GPTQHIP_EINVAL;
+    }
+    return GPTQHIP_OK;
+}
+
+// ---- FP8 experts: shapes and scale layouts (few-token and grouped ops) ------------------------------------------------------------------------
+// the scale layout of one stacked projection [N, K]: nullptr when served
+inline const char* moe_fp8_scale_error(int K, int N, int mode, int br, int bc) {
+    if (mode == GPTQHIP_FP8_SCALE_TENSOR || mode == GPTQHIP_FP8_SCALE_ROW) return nullptr;
+    if (mode != GPTQHIP_FP8_SCALE_BLOCK) return "scale layout must be tensor (0), row (1) or block (2)";
+    if (bc <= 0 || bc % kChunkK != 0 || K % bc != 0) return "block columns must be a multiple of 128 dividing in_features";
+    if (br <= 0 || N % br != 0) return "block rows must divide out_features";
+    return nullptr;
+}
+
+// experts H x I with these scale layouts and activations, whatever the number of tokens
+inline bool moe_fp8_layouts_ok(int H, int I, int gate_up_block_cols, int down_scale_mode, int down_block_rows, int down_block_cols, int act_dtype) {
+    if (act_dtype != GPTQHIP_FP16 && act_dtype != GPTQHIP_BF16) return false;
+    if (!(H > 0 && I > 0 && H % 128 == 0 && I % 128 == 0)) return false;
+    if (gate_up_block_cols != 0 && moe_fp8_scale_error(H, 2 * I, GPTQHIP_FP8_SCALE_BLOCK, 1, gate_up_block_cols) != nullptr) return false;
+    return moe_fp8_scale_error(I, H, down_scale_mode, down_block_rows, down_block_cols) == nullptr;
+}
+
+// K, N, mode, br, bc: the projection the call runs
+inline int moe_check_fp8_shape(const char* fn, int H, int I, int K, int N, int mode, int br, int bc, int act_dtype) {
+    if (H <= 0 || I <= 0 || H % 128 != 0 || I % 128 != 0) {
+        set_error("%s: unsupported shape H=%d I=%d (H and I positive multiples of 128)", fn, H, I);
+        return GPTQHIP_EINVAL;
+    }
+    if (const char* why = moe_fp8_scale_error(K, N, mode, br, bc)) {
+        set_error("%s: %s (in_features=%d out_features=%d scale layout %d block %d x %d)", fn, why, K, N, mode, br, bc);
+        return GPTQHIP_EINVAL;
+    }
+    if (act_dtype != GPTQHIP_FP16 && act_dtype != GPTQHIP_BF16) {
+        set_error("%s: unsupported activation dtype tag %d (fp16 = 0, bf16 = 1)", fn, act_dtype);
+        return GPTQHIP_EINVAL;
+    }
+    return GPTQHIP_OK;
 }
 
 }  // namespace gptqhip

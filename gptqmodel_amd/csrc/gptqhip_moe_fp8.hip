@@ -142,38 +142,13 @@ __global__ __launch_bounds__(64 * kMoeDownWaves) void moe_fp8_down_kernel(MoeFp8
                            [&](float d, int ej) { return BLOCK ? d : d * p.rs[down_scale_index(p, ej, n)]; });
 }
 
-// the scale layout of one stacked projection [N, K]: nullptr when served
-static const char* moe_fp8_scale_error(int K, int N, int mode, int br, int bc) {
-    if (mode == GPTQHIP_FP8_SCALE_TENSOR || mode == GPTQHIP_FP8_SCALE_ROW) return nullptr;
-    if (mode != GPTQHIP_FP8_SCALE_BLOCK) return "scale layout must be tensor (0), row (1) or block (2)";
-    if (bc <= 0 || bc % kChunkK != 0 || K % bc != 0) return "block columns must be a multiple of 128 dividing in_features";
-    if (br <= 0 || N % br != 0) return "block rows must divide out_features";
-    return nullptr;
-}
-
-static bool moe_fp8_dims_ok(int H, int I, int T, int top_k) {
-    return H > 0 && I > 0 && H % 128 == 0 && I % 128 == 0 && moe_few_tokens_ok(T, top_k);
-}
-
 // K, N, mode, br, bc: the projection the call runs
 static int moe_fp8_validate(const char* fn, const void* const* ptrs16, int n16, const void* const* ptrs4, int n4, int T, int top_k, int E, int H, int I,
                             int K, int N, int mode, int br, int bc, int act_dtype) {
     int rc = moe_check_ptrs(fn, ptrs16, n16, "activations, weights and outputs", ptrs4, n4, "reciprocal scales, ids, routing weights and status");
     if (!rc) rc = moe_check_few_tokens(fn, T, top_k, E);
     if (rc) return rc;
-    if (H <= 0 || I <= 0 || H % 128 != 0 || I % 128 != 0) {
-        set_error("%s: unsupported shape H=%d I=%d (H and I positive multiples of 128)", fn, H, I);
-        return GPTQHIP_EINVAL;
-    }
-    if (const char* why = moe_fp8_scale_error(K, N, mode, br, bc)) {
-        set_error("%s: %s (in_features=%d out_features=%d scale layout %d block %d x %d)", fn, why, K, N, mode, br, bc);
-        return GPTQHIP_EINVAL;
-    }
-    if (act_dtype != GPTQHIP_FP16 && act_dtype != GPTQHIP_BF16) {
-        set_error("%s: unsupported activation dtype tag %d (fp16 = 0, bf16 = 1)", fn, act_dtype);
-        return GPTQHIP_EINVAL;
-    }
-    return GPTQHIP_OK;
+    return moe_check_fp8_shape(fn, H, I, K, N, mode, br, bc, act_dtype);
 }
 
 static MoeFp8Params moe_fp8_params(const void* x, const uint8_t* wt, const float* rs, const int32_t* ids, const float* weights, void* out,
@@ -210,10 +185,7 @@ extern "C" {
 
 int gptqhip_moe_fp8_supported(int H, int I, int gate_up_block_cols, int down_scale_mode, int down_block_rows, int down_block_cols, int T, int top_k,
                               int act_dtype) {
-    if (act_dtype != GPTQHIP_FP16 && act_dtype != GPTQHIP_BF16) return 0;
-    if (!moe_fp8_dims_ok(H, I, T, top_k)) return 0;
-    if (gate_up_block_cols != 0 && moe_fp8_scale_error(H, 2 * I, GPTQHIP_FP8_SCALE_BLOCK, 1, gate_up_block_cols) != nullptr) return 0;
-    return moe_fp8_scale_error(I, H, down_scale_mode, down_block_rows, down_block_cols) == nullptr ? 1 : 0;
+    return moe_fp8_layouts_ok(H, I, gate_up_block_cols, down_scale_mode, down_block_rows, down_block_cols, act_dtype) && moe_few_tokens_ok(T, top_k) ? 1 : 0;
 }
 
 int gptqhip_moe_fp8_gate_up(const void* x, const uint8_t* weight_t, const float* rscale, const int32_t* ids, void* act, int32_t* status, int T,

@@ -24,20 +24,11 @@
 
 namespace gptqhip {
 
+// (kUnitRows, grouped_units, the routing limits and their checks: gptqhip_moe_common.h, shared with gptqhip_moe_fp8_grouped.hip)
 constexpr int kAlignWaves = 16;            // waves of the align block
-constexpr int kGroupedMaxExperts = 512;    // cnt[16][E] ints of LDS: 32 KiB at E = 512
-constexpr int kGroupedMaxSlots = 65536;    // max_units <= 4576 blocks in grid.y
-constexpr int kGroupedMaxTopK = 16;
 constexpr int kGroupedGateUpWaves = 8;
 constexpr int kGroupedDownWaves = 16;
 constexpr int kGroupedAhead = 2;           // chunks whose loads a wave issues before consuming the first
-constexpr int kUnitRows = 16;
-
-__host__ __device__ inline int grouped_units(int S, int E) {
-    const int ne = S < E ? S : E;
-    const int u = (S + 15 * ne) / 16;
-    return u < S ? u : S;
-}
 
 struct AlignParams {
     const int32_t* ids;
@@ -228,24 +219,6 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(CombineParams p) {
         o.y = pack_bf16(y[2], y[3]);
     }
     *reinterpret_cast<u2_t*>(p.out + (size_t)t * p.H + col) = o;
-}
-
-static bool grouped_routing_ok(int T, int top_k, int E) {
-    return T >= 1 && top_k >= 1 && top_k <= kGroupedMaxTopK && E >= 1 && E <= kGroupedMaxExperts && (long long)T * top_k <= kGroupedMaxSlots;
-}
-
-static int grouped_check_ptrs(const char* fn, const void* const* ptrs16, int n16, const void* const* ptrs4, int n4) {
-    return moe_check_ptrs(fn, ptrs16, n16, "activations, weights, constants, partial sums and outputs", ptrs4, n4,
-                          "ids, weights, sort buffers and status");
-}
-
-static int grouped_check_routing(const char* fn, int T, int top_k, int E) {
-    if (!grouped_routing_ok(T, top_k, E)) {
-        set_error("%s: T=%d top_k=%d E=%d outside T >= 1, 1 <= top_k <= %d, 1 <= E <= %d, T * top_k <= %d", fn, T, top_k, E, kGroupedMaxTopK,
-                  kGroupedMaxExperts, kGroupedMaxSlots);
-        return GPTQHIP_EINVAL;
-    }
-    return GPTQHIP_OK;
 }
 
 template <bool GATE_UP, int MAXW>

@@ -7,8 +7,8 @@ call signature of transformers' experts modules (Qwen3MoeExperts.forward / Mixtr
 
     forward(hidden_states [T, H], top_k_index [T, k], top_k_weights [T, k]) -> [T, H]
 
-The call checks, the device-routed fast path, the status word and the host-routed slow path are StackedMoeExperts' (nn_modules/moe_base.py, which
-states the rounding contract); this module adds the 4-bit stacking and:
+The call checks, the device-routed fast path, the grouped path's window, buffers and capture rule, the status word and the host-routed slow path are
+StackedMoeExperts' (nn_modules/moe_base.py, which states the rounding contract); this module adds the 4-bit stacking and:
 
 * fast path (ops.moe_supported: 4 bits, group_size = 128 * 2^n, no act-order, T <= 16, top_k <= 16): gptqhip_moe_gate_up + gptqhip_moe_down.
 * grouped path (ops.moe_grouped_supported: the same shapes at ANY T): gptqhip_moe_align + gptqhip_moe_gate_up_grouped + gptqhip_moe_down_grouped
@@ -21,8 +21,7 @@ states the rounding contract); this module adds the 4-bit stacking and:
 """
 from __future__ import annotations
 
-import os
-from typing import Dict, Sequence, Tuple
+from typing import Dict, Sequence
 
 import torch
 import torch.nn as nn
@@ -52,6 +51,7 @@ def _interleave_tiled(gate: torch.Tensor, up: torch.Tensor, tiles: int, inner: i
 class HipMoeExperts(StackedMoeExperts):
     _SOURCE_KIND = "HIP GPTQ linear"
     _RELEASE_NAMES = ("qweight", "qzeros", "scales", "g_idx", "meta")
+    GROUPED_WINDOW = (GROUPED_MIN_TOKENS, GROUPED_MAX_TOKENS)
 
     def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, gate_up_group_size: int, down_group_size: int,
                  scale_dtype: torch.dtype):
@@ -60,12 +60,6 @@ class HipMoeExperts(StackedMoeExperts):
         self.down_group_size = down_group_size
         self.scale_dtype = scale_dtype
         self.bits = 4
-        self.grouped_routing = os.environ.get("GPTQHIP_MOE_GROUPED", "0") == "1"
-        self.grouped_min_tokens = GROUPED_MIN_TOKENS
-        self.grouped_max_tokens = GROUPED_MAX_TOKENS
-        self._grouped_ok: Dict[Tuple[int, int], bool] = {}
-        self._grouped_eager: Dict[Tuple, Dict] = {}        # (dtype, device) -> one grow-only buffer set, sliced per call
-        self._grouped_captured: Dict[Tuple, Tuple[torch.Tensor, ...]] = {}      # (T, top_k, dtype, device) -> buffers a graph holds: never freed
 
     @staticmethod
     def _is_source(m) -> bool:
@@ -163,53 +157,13 @@ class HipMoeExperts(StackedMoeExperts):
             self._grouped_ok[key] = ok
         return ok and self._dtype_ok(dtype)
 
-    def _grouped_alloc(self, S: int, T: int, dtype: torch.dtype, device: torch.device) -> Dict:
-        units = ops.moe_grouped_units(S, self.num_experts)
-        i32 = dict(dtype=torch.int32, device=device)
-        return {"S": S, "T": T,
-                "ids": torch.empty(S, **i32), "w": torch.empty(S, dtype=torch.float32, device=device),
-                "sorted": torch.empty(16 * units, **i32), "unit_expert": torch.empty(units, **i32), "num_units": torch.empty(1, **i32),
-                "act": torch.empty(S * self.intermediate_dim, dtype=dtype, device=device),
-                "part": torch.empty(S * self.hidden_dim, dtype=torch.float32, device=device),
-                "out": torch.empty(T * self.hidden_dim, dtype=dtype, device=device)}
+    def _grouped_gate_up(self, x: torch.Tensor, b: Dict, act: torch.Tensor, top_k: int) -> None:
+        ops.moe_gate_up_grouped(x, self.gate_up_qweight, self.gate_up_meta, b["sorted"], b["unit_expert"], b["num_units"], act, top_k,
+                                self.num_experts, self.intermediate_dim, self.gate_up_group_size, self.scale_dtype)
 
-    def _grouped_scratch(self, T: int, top_k: int, dtype: torch.dtype, device: torch.device, capturing: bool) -> Dict:
-        S = T * top_k
-        if capturing:       # a graph holds these pointers: one set per signature, never freed or reallocated
-            key = (T, top_k, dtype, device)
-            b = self._grouped_captured.get(key)
-            if b is None:
-                b = self._grouped_captured[key] = self._grouped_alloc(S, T, dtype, device)
-            return b
-        key = (dtype, device)
-        b = self._grouped_eager.get(key)
-        if b is None or b["S"] < S or b["T"] < T:       # grow only: a prefill's varying T shares one set
-            b = self._grouped_eager[key] = self._grouped_alloc(max(S, b["S"] if b else 0), max(T, b["T"] if b else 0), dtype, device)
-        return b
-
-    def _forward_grouped(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor, capturing: bool) -> torch.Tensor:
-        """The four expert-grouped launches.  The result lives in a persistent buffer of this module that the next grouped call overwrites
-        (eager calls share one grow-only buffer set; a captured call owns the set of its (T, top_k, dtype) signature)."""
-        T, top_k = top_k_index.shape
-        S, H, I, E = T * top_k, self.hidden_dim, self.intermediate_dim, self.num_experts
-        b = self._grouped_scratch(T, top_k, hidden_states.dtype, hidden_states.device, capturing)
-        x, ids, w = self._device_routing(hidden_states, top_k_index, top_k_weights, b["ids"], b["w"])
-        act, part, out = b["act"][:S * I].view(S, I), b["part"][:S * H].view(S, H), b["out"][:T * H].view(T, H)
-        ops.moe_align(ids, b["sorted"], b["unit_expert"], b["num_units"], self.status, E)
-        ops.moe_gate_up_grouped(x, self.gate_up_qweight, self.gate_up_meta, b["sorted"], b["unit_expert"], b["num_units"], act, top_k, E, I,
-                                self.gate_up_group_size, self.scale_dtype)
-        ops.moe_down_grouped(act, self.down_qweight, self.down_meta, b["sorted"], b["unit_expert"], b["num_units"], part, top_k, E, H,
-                             self.down_group_size, self.scale_dtype)
-        ops.moe_combine(part, ids, w, out, self.status, E)
-        return out
-
-    def _forward_routed(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
-        T, top_k = top_k_index.shape
-        if self.grouped_routing and self.grouped_min_tokens <= T <= self.grouped_max_tokens and self.grouped_path(T, top_k, hidden_states.dtype):
-            return self._forward_grouped(hidden_states, top_k_index, top_k_weights, torch.cuda.is_current_stream_capturing())
-        if T > MAX_FAST_TOKENS and torch.cuda.is_current_stream_capturing() and self.grouped_path(T, top_k, hidden_states.dtype):
-            return self._forward_grouped(hidden_states, top_k_index, top_k_weights, True)      # the host-routed loop cannot be captured
-        return super()._forward_routed(hidden_states, top_k_index, top_k_weights)
+    def _grouped_down(self, act: torch.Tensor, b: Dict, part: torch.Tensor, top_k: int) -> None:
+        ops.moe_down_grouped(act, self.down_qweight, self.down_meta, b["sorted"], b["unit_expert"], b["num_units"], part, top_k, self.num_experts,
+                             self.hidden_dim, self.down_group_size, self.scale_dtype)
 
     def _fused_gate_up(self, x: torch.Tensor, ids: torch.Tensor, act: torch.Tensor) -> None:
         ops.moe_gate_up(x, self.gate_up_qweight, self.gate_up_meta, ids, act, self.status, self.num_experts, self.intermediate_dim,

@@ -11,20 +11,28 @@ experts modules (Qwen3MoeExperts.forward / MixtralExperts.forward):
   word, which check_status() reads (never forward()).  Rounding: each projection and the SiLU chain as the per-expert modules round them; the
   top_k expert outputs are combined in ONE fp32 weighted sum in slot order and rounded once (csrc/gptqhip_moe_common.h states both contracts),
   where the HF loop rounds every expert's output and every product and accumulates in the activation dtype.
+* grouped path (the subclass's grouped_path predicate: the same shapes at ANY T): gptqhip_moe_align + the subclass's two expert-grouped stages
+  + gptqhip_moe_combine -- the slots sorted by expert on the device, every 16-row unit of one expert on the matrix pipe, the same combine
+  contract (one fp32 weighted sum in slot order, one rounding), the same status word, no host synchronisation.  Taken when `grouped_routing`
+  is set and grouped_min_tokens <= T <= grouped_max_tokens (off by default; GPTQHIP_MOE_GROUPED=1 at construction turns it on), and for
+  T > 16 under stream capture, where the host-routed loop cannot run at all.
 * slow path (_forward_loop: more tokens, other shapes or dtypes): the host-routed per-expert loop of the HF module over views into the same
   stacked buffers -- arithmetically what a loop over the original modules does.
 
 A subclass supplies the kind of linear it stacks (_is_source / _SOURCE_KIND / _RELEASE_NAMES), the stacking itself (from_linears, on the checks
-of _check_lists / _check_module), the fast_path predicate, the two fused op calls (_fused_gate_up / _fused_down) and the slow loop's per-expert
-gemm (_expert_gemm).
+of _check_lists / _check_module), the fast_path and grouped_path predicates, the two fused op calls (_fused_gate_up / _fused_down), the two
+grouped stage calls (_grouped_gate_up / _grouped_down), its eager grouped window (GROUPED_WINDOW) and the slow loop's per-expert gemm
+(_expert_gemm).
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, List, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
+from .. import ops
 from ..utils.model import deinterleave_gate_up
 
 MAX_FAST_TOKENS = 16
@@ -33,6 +41,9 @@ MAX_FAST_TOKENS = 16
 class StackedMoeExperts(nn.Module):
     _SOURCE_KIND = ""                      # "HIP GPTQ linear": the per-expert module from_linears takes, as messages name it
     _RELEASE_NAMES: Tuple[str, ...] = ()   # its device tensors, dropped once stacked
+    # eager window of the grouped path when grouped_routing is set: the first T the few-token ops do not serve, and the grouped ops' slot limit
+    # (structural; a subclass states the window its own measurement gives)
+    GROUPED_WINDOW: Tuple[int, int] = (MAX_FAST_TOKENS + 1, 65536)
 
     def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int):
         super().__init__()
@@ -42,6 +53,11 @@ class StackedMoeExperts(nn.Module):
         self.training = False
         self._scratch: Dict[Tuple, Tuple[torch.Tensor, ...]] = {}
         self._fast_ok: Dict[Tuple[int, int], bool] = {}
+        self.grouped_routing = os.environ.get("GPTQHIP_MOE_GROUPED", "0") == "1"
+        self.grouped_min_tokens, self.grouped_max_tokens = self.GROUPED_WINDOW
+        self._grouped_ok: Dict[Tuple[int, int], bool] = {}
+        self._grouped_eager: Dict[Tuple, Dict] = {}        # (dtype, device) -> one grow-only buffer set, sliced per call
+        self._grouped_captured: Dict[Tuple, Dict] = {}     # (T, top_k, dtype, device) -> buffers a graph holds: never freed
 
     def train(self, mode: bool = True):
         if mode:      # the quantised linears it is built from refuse training mode the same way (SUPPORTS_TRAINING = False)
@@ -94,6 +110,18 @@ class StackedMoeExperts(nn.Module):
         """x @ expert e's `gate_up` | `down` projection, through the op the per-expert module would call, on views into the stacked buffers."""
         raise NotImplementedError
 
+    def grouped_path(self, T: int, top_k: int, dtype: torch.dtype) -> bool:
+        """Whether the expert-grouped ops can serve this call (the shape predicate; forward() takes them only inside the grouped_routing window
+        or under stream capture)."""
+        raise NotImplementedError
+
+    def _grouped_gate_up(self, x: torch.Tensor, b: Dict, act: torch.Tensor, top_k: int) -> None:
+        """Stage one on the sort buffers b["sorted"] / b["unit_expert"] / b["num_units"]."""
+        raise NotImplementedError
+
+    def _grouped_down(self, act: torch.Tensor, b: Dict, part: torch.Tensor, top_k: int) -> None:
+        raise NotImplementedError
+
     def _scratch_for(self, T: int, top_k: int, dtype: torch.dtype, device: torch.device):
         key = (T, top_k, dtype)
         s = self._scratch.get(key)
@@ -122,6 +150,44 @@ class StackedMoeExperts(nn.Module):
             w.copy_(top_k_weights)
         return hidden_states if hidden_states.is_contiguous() else hidden_states.contiguous(), ids, w
 
+    def _grouped_alloc(self, S: int, T: int, dtype: torch.dtype, device: torch.device) -> Dict:
+        units = ops.moe_grouped_units(S, self.num_experts)
+        i32 = dict(dtype=torch.int32, device=device)
+        return {"S": S, "T": T,
+                "ids": torch.empty(S, **i32), "w": torch.empty(S, dtype=torch.float32, device=device),
+                "sorted": torch.empty(16 * units, **i32), "unit_expert": torch.empty(units, **i32), "num_units": torch.empty(1, **i32),
+                "act": torch.empty(S * self.intermediate_dim, dtype=dtype, device=device),
+                "part": torch.empty(S * self.hidden_dim, dtype=torch.float32, device=device),
+                "out": torch.empty(T * self.hidden_dim, dtype=dtype, device=device)}
+
+    def _grouped_scratch(self, T: int, top_k: int, dtype: torch.dtype, device: torch.device, capturing: bool) -> Dict:
+        S = T * top_k
+        if capturing:       # a graph holds these pointers: one set per signature, never freed or reallocated
+            key = (T, top_k, dtype, device)
+            b = self._grouped_captured.get(key)
+            if b is None:
+                b = self._grouped_captured[key] = self._grouped_alloc(S, T, dtype, device)
+            return b
+        key = (dtype, device)
+        b = self._grouped_eager.get(key)
+        if b is None or b["S"] < S or b["T"] < T:       # grow only: a prefill's varying T shares one set
+            b = self._grouped_eager[key] = self._grouped_alloc(max(S, b["S"] if b else 0), max(T, b["T"] if b else 0), dtype, device)
+        return b
+
+    def _forward_grouped(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor, capturing: bool) -> torch.Tensor:
+        """The four expert-grouped launches.  The result lives in a persistent buffer of this module that the next grouped call overwrites
+        (eager calls share one grow-only buffer set; a captured call owns the set of its (T, top_k, dtype) signature)."""
+        T, top_k = top_k_index.shape
+        S, H, I, E = T * top_k, self.hidden_dim, self.intermediate_dim, self.num_experts
+        b = self._grouped_scratch(T, top_k, hidden_states.dtype, hidden_states.device, capturing)
+        x, ids, w = self._device_routing(hidden_states, top_k_index, top_k_weights, b["ids"], b["w"])
+        act, part, out = b["act"][:S * I].view(S, I), b["part"][:S * H].view(S, H), b["out"][:T * H].view(T, H)
+        ops.moe_align(ids, b["sorted"], b["unit_expert"], b["num_units"], self.status, E)
+        self._grouped_gate_up(x, b, act, top_k)
+        self._grouped_down(act, b, part, top_k)
+        ops.moe_combine(part, ids, w, out, self.status, E)
+        return out
+
     def forward(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
         if hidden_states.dim() != 2 or hidden_states.shape[1] != self.hidden_dim or top_k_index.dim() != 2 \
                 or top_k_index.shape != top_k_weights.shape or top_k_index.shape[0] != hidden_states.shape[0]:
@@ -134,8 +200,13 @@ class StackedMoeExperts(nn.Module):
         return self._forward_routed(hidden_states, top_k_index, top_k_weights)
 
     def _forward_routed(self, hidden_states: torch.Tensor, top_k_index: torch.Tensor, top_k_weights: torch.Tensor) -> torch.Tensor:
-        """A validated call with T >= 1: the two fused launches where fast_path() holds, else the host-routed loop."""
+        """A validated call with T >= 1: the grouped launches inside the grouped_routing window and for T > 16 under capture, the two fused
+        launches where fast_path() holds, else the host-routed loop."""
         T, top_k = top_k_index.shape
+        if self.grouped_routing and self.grouped_min_tokens <= T <= self.grouped_max_tokens and self.grouped_path(T, top_k, hidden_states.dtype):
+            return self._forward_grouped(hidden_states, top_k_index, top_k_weights, torch.cuda.is_current_stream_capturing())
+        if T > MAX_FAST_TOKENS and torch.cuda.is_current_stream_capturing() and self.grouped_path(T, top_k, hidden_states.dtype):
+            return self._forward_grouped(hidden_states, top_k_index, top_k_weights, True)      # the host-routed loop cannot be captured
         if T > MAX_FAST_TOKENS or not self.fast_path(T, top_k, hidden_states.dtype):
             return self._forward_loop(hidden_states, top_k_index, top_k_weights)
         # the result lives in a persistent buffer of this module (one per (T, top_k, dtype)): the next call with that signature overwrites it

@@ -17,22 +17,32 @@ Stacked layout (fixed by from_linears, on the device):
   down_weight uint8 [E, I * H], down_rscale fp32 [E, 1] | [E, H] | [E, H / br, I / bc]: the module's native layout, not interleaved.
 The reciprocals are the ones gptqhip_fp8_repack forms (IEEE fp32 division, once).
 
-The call checks, the device-routed fast path, the status word and the host-routed slow path are StackedMoeExperts' (nn_modules/moe_base.py, which
-states the rounding contract); this module adds the FP8 stacking and:
+The call checks, the device-routed fast path, the grouped path's window, buffers and capture rule, the status word and the host-routed slow path are
+StackedMoeExperts' (nn_modules/moe_base.py, which states the rounding contract); this module adds the FP8 stacking and:
 
 * fast path (ops.moe_fp8_supported: H % 128 == 0, I % 128 == 0, T <= 16, top_k <= 16, fp16 | bf16): gptqhip_moe_fp8_gate_up + gptqhip_moe_fp8_down.
-* slow path (more tokens, other dtypes): the host-routed per-expert loop of the HF module on ops.fp8_gemm over views into the same stacked
-  buffers -- arithmetically what a loop over the original HipFp8Linear modules does.
-The expert-grouped path of HipMoeExperts has no FP8 counterpart."""
+* grouped path (ops.moe_fp8_grouped_supported: the same shapes and scale layouts at ANY T, top_k <= 16, E <= 512, T * top_k <= 65536):
+  gptqhip_moe_align + gptqhip_moe_fp8_gate_up_grouped + gptqhip_moe_fp8_down_grouped + gptqhip_moe_combine on the same stacked buffers.  Taken
+  when `grouped_routing` is set and grouped_min_tokens <= T <= grouped_max_tokens (off by default; GPTQHIP_MOE_GROUPED=1 at construction turns
+  it on), and for T > 16 under stream capture: FP8 MoE prefill and large-batch decode inside torch.cuda.graph.  Same contract as the fast path,
+  another K summation order: the two agree within the bar, not bit for bit.
+* slow path (more tokens with the flag off, other dtypes): the host-routed per-expert loop of the HF module on ops.fp8_gemm over views into the
+  same stacked buffers -- arithmetically what a loop over the original HipFp8Linear modules does."""
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from .. import ops
 from .moe_base import MAX_FAST_TOKENS, StackedMoeExperts
+
+# eager window of the grouped path when grouped_routing is set, MEASURED (DESIGN.md 4.6.1, profiles/r14_moe_fp8_grouped.txt, the rule of 4.4.1):
+# the smallest T from which grouped eager is not slower than the few-token ops on Qwen3-30B-A3B and Mixtral-8x7B, and the largest measured T at
+# which it is not slower than the host loop on both (on Mixtral the two meet there).  tests/dev/moe_fp8_grouped_probe.py prints both.
+GROUPED_MIN_TOKENS = 16
+GROUPED_MAX_TOKENS = 1024
 
 
 def interleave_rows8(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
@@ -67,6 +77,7 @@ def _scale_rows(s: torch.Tensor, method: str, block: Optional[Tuple[int, int]], 
 class HipFp8MoeExperts(StackedMoeExperts):
     _SOURCE_KIND = "HIP FP8 linear"
     _RELEASE_NAMES = ("weight", "weight_scale_inv", "rscale")
+    GROUPED_WINDOW = (GROUPED_MIN_TOKENS, GROUPED_MAX_TOKENS)
 
     def __init__(self, num_experts: int, hidden_dim: int, intermediate_dim: int, gate_up_scale_method: str,
                  gate_up_block_size: Optional[Tuple[int, int]], down_scale_method: str, down_block_size: Optional[Tuple[int, int]]):
@@ -189,6 +200,27 @@ class HipFp8MoeExperts(StackedMoeExperts):
             ok = ops.moe_fp8_supported(self.hidden_dim, self.intermediate_dim, self.gate_up_block_cols, mode, block, T, top_k, torch.float16)
             self._fast_ok[key] = ok
         return ok and dtype in (torch.float16, torch.bfloat16)
+
+    def grouped_path(self, T: int, top_k: int, dtype: torch.dtype) -> bool:
+        """Whether the expert-grouped ops can serve this call (the shape predicate; forward() takes them only inside the grouped_routing window
+        or under stream capture)."""
+        key = (T, top_k)
+        ok = self._grouped_ok.get(key)
+        if ok is None:
+            mode, block = self._down_mode()
+            ok = ops.moe_fp8_grouped_supported(self.hidden_dim, self.intermediate_dim, self.gate_up_block_cols, mode, block, T, top_k,
+                                               self.num_experts, torch.float16)
+            self._grouped_ok[key] = ok
+        return ok and dtype in (torch.float16, torch.bfloat16)
+
+    def _grouped_gate_up(self, x: torch.Tensor, b: Dict, act: torch.Tensor, top_k: int) -> None:
+        ops.moe_fp8_gate_up_grouped(x, self.gate_up_weight, self.gate_up_rscale, b["sorted"], b["unit_expert"], b["num_units"], act, top_k,
+                                    self.num_experts, self.intermediate_dim, self.gate_up_block_cols)
+
+    def _grouped_down(self, act: torch.Tensor, b: Dict, part: torch.Tensor, top_k: int) -> None:
+        mode, block = self._down_mode()
+        ops.moe_fp8_down_grouped(act, self.down_weight, self.down_rscale, b["sorted"], b["unit_expert"], b["num_units"], part, top_k,
+                                 self.num_experts, self.hidden_dim, mode, block)
 
     def _fused_gate_up(self, x: torch.Tensor, ids: torch.Tensor, act: torch.Tensor) -> None:
         ops.moe_fp8_gate_up(x, self.gate_up_weight, self.gate_up_rscale, ids, act, self.status, self.num_experts, self.intermediate_dim,

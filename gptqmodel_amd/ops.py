@@ -541,15 +541,20 @@ def moe_fp8_supported(H: int, I: int, gate_up_block_cols: int = 0, down_scale_mo
     return bool(_lib.load().gptqhip_moe_fp8_supported(H, I, int(gate_up_block_cols), down_scale_mode, br, bc, T, top_k, _DT.get(dtype, -1)))
 
 
+def _moe_fp8_stacked_check(what: str, weight_t: torch.Tensor, rscale: torch.Tensor, E: int, w_bytes: int, n_scales: int):
+    """The stacked weights / reciprocal scales of every FP8 MoE stage, few-token and grouped."""
+    if weight_t.dtype != torch.uint8 or weight_t.numel() != E * w_bytes or not weight_t.is_contiguous():
+        raise RuntimeError(f"{what}: weight_t must be a contiguous uint8 tensor of E * {w_bytes} bytes")
+    if rscale.dtype != torch.float32 or rscale.numel() != E * n_scales or not rscale.is_contiguous():
+        raise RuntimeError(f"{what}: rscale must be a contiguous float32 tensor of E * {n_scales} elements")
+
+
 def _moe_fp8_check(what: str, x: torch.Tensor, rows: int, cols: int, ids: torch.Tensor, status: torch.Tensor, weight_t: torch.Tensor,
                    rscale: torch.Tensor, E: int, w_bytes: int, n_scales: int):
     if x.dtype not in _DT:
         raise RuntimeError(f"{what}: unsupported activation dtype {x.dtype}")
     _moe_io_check(what, x, rows, cols, ids, status)
-    if weight_t.dtype != torch.uint8 or weight_t.numel() != E * w_bytes or not weight_t.is_contiguous():
-        raise RuntimeError(f"{what}: weight_t must be a contiguous uint8 tensor of E * {w_bytes} bytes")
-    if rscale.dtype != torch.float32 or rscale.numel() != E * n_scales or not rscale.is_contiguous():
-        raise RuntimeError(f"{what}: rscale must be a contiguous float32 tensor of E * {n_scales} elements")
+    _moe_fp8_stacked_check(what, weight_t, rscale, E, w_bytes, n_scales)
 
 
 def moe_fp8_gate_up(x: torch.Tensor, weight_t: torch.Tensor, rscale: torch.Tensor, ids: torch.Tensor, act: torch.Tensor, status: torch.Tensor,
@@ -594,6 +599,66 @@ def moe_fp8_down(act: torch.Tensor, weight_t: torch.Tensor, rscale: torch.Tensor
                                               E, H, I, scale_mode, br, bc, _DT[act.dtype], _stream(act.device))
     _lib.check(rc, "gptqhip_moe_fp8_down")
     return out
+
+
+def moe_fp8_grouped_supported(H: int, I: int, gate_up_block_cols: int = 0, down_scale_mode: int = FP8_SCALE_ROW, down_block_size=None, T: int = 1,
+                              top_k: int = 1, E: int = 1, dtype: torch.dtype = torch.float16) -> bool:
+    """True when the expert-grouped FP8 MoE ops (moe_align / moe_fp8_gate_up_grouped / moe_fp8_down_grouped / moe_combine) serve E experts with
+    hidden size H and intermediate size I for T tokens x top_k slots (gptqhip_moe_fp8_grouped_supported: host logic, no GPU): the shape and
+    scale rules of moe_fp8_supported at ANY T, within the routing limits of the grouped ops."""
+    br, bc = (0, 0) if down_scale_mode != FP8_SCALE_BLOCK or down_block_size is None else (int(down_block_size[0]), int(down_block_size[1]))
+    return bool(_lib.load().gptqhip_moe_fp8_grouped_supported(H, I, int(gate_up_block_cols), down_scale_mode, br, bc, T, top_k, E,
+                                                              _DT.get(dtype, -1)))
+
+
+def _moe_fp8_grouped_check(what: str, x: torch.Tensor, weight_t: torch.Tensor, rscale: torch.Tensor, E: int, w_bytes: int, n_scales: int):
+    """_moe_fp8_check on a grouped stage, whose input has no ids / status beside it."""
+    if x.dtype not in _DT or x.dim() != 2 or not x.is_contiguous():
+        raise RuntimeError(f"{what}: input must be a contiguous 16-bit 2-D tensor (got {x.dtype} {tuple(x.shape)})")
+    _moe_fp8_stacked_check(what, weight_t, rscale, E, w_bytes, n_scales)
+
+
+def moe_fp8_gate_up_grouped(x: torch.Tensor, weight_t: torch.Tensor, rscale: torch.Tensor, sorted_slots: torch.Tensor, unit_expert: torch.Tensor,
+                            num_units: torch.Tensor, act: torch.Tensor, top_k: int, E: int, I: int, block_cols: int = 0) -> torch.Tensor:
+    """Stage one on the sorted slots (gptqhip_moe_fp8_gate_up_grouped): act[s, :I] of every slot in a unit, the rounding chain of
+    moe_fp8_gate_up.  x [T, H]; weight_t / rscale: the stacked buffers of moe_fp8_gate_up; act: >= T * top_k * I elements of x.dtype (rows of
+    slots in no unit are left untouched)."""
+    _require_cuda(x, weight_t, rscale, sorted_slots, unit_expert, num_units, act)
+    bc = int(block_cols)
+    H = x.shape[-1]
+    _moe_fp8_grouped_check("moe_fp8_gate_up_grouped", x, weight_t, rscale, E, 2 * I * H, 2 * I * (H // bc if bc > 0 else 1))
+    T = x.shape[0]
+    _moe_sort_check("moe_fp8_gate_up_grouped", T * top_k, E, sorted_slots, unit_expert, num_units)
+    if act.dtype != x.dtype or act.numel() < T * top_k * I or not act.is_contiguous():
+        raise RuntimeError(f"moe_fp8_gate_up_grouped: act must be a contiguous {x.dtype} tensor with >= {T * top_k * I} elements")
+    with torch.cuda.device(x.device):
+        rc = _lib.load().gptqhip_moe_fp8_gate_up_grouped(_ptr(x), _ptr(weight_t), _ptr(rscale), _ptr(sorted_slots), _ptr(unit_expert),
+                                                         _ptr(num_units), _ptr(act), T, top_k, E, H, I, bc, _DT[x.dtype], _stream(x.device))
+    _lib.check(rc, "gptqhip_moe_fp8_gate_up_grouped")
+    return act
+
+
+def moe_fp8_down_grouped(act: torch.Tensor, weight_t: torch.Tensor, rscale: torch.Tensor, sorted_slots: torch.Tensor, unit_expert: torch.Tensor,
+                         num_units: torch.Tensor, part: torch.Tensor, top_k: int, E: int, H: int, scale_mode: int, block_size=None) -> torch.Tensor:
+    """Stage two on the sorted slots (gptqhip_moe_fp8_down_grouped): part[s, :H] = act[s] @ the down weight of the slot's expert, UNROUNDED fp32
+    with the reciprocal scales applied; moe_combine finishes it.  act [T * top_k, I]; weight_t / rscale: the stacked buffers of moe_fp8_down;
+    part: >= T * top_k * H float32 elements."""
+    _require_cuda(act, weight_t, rscale, sorted_slots, unit_expert, num_units, part)
+    br, bc = _fp8_block(scale_mode, block_size)
+    I = act.shape[-1]
+    _moe_fp8_grouped_check("moe_fp8_down_grouped", act, weight_t, rscale, E, I * H, _fp8_scale_count(I, H, scale_mode, br, bc))
+    S = act.shape[0]
+    if top_k < 1 or S % top_k != 0:
+        raise RuntimeError(f"moe_fp8_down_grouped: act must have T * top_k rows (got {S} rows, top_k = {top_k})")
+    _moe_sort_check("moe_fp8_down_grouped", S, E, sorted_slots, unit_expert, num_units)
+    if part.dtype != torch.float32 or part.numel() < S * H or not part.is_contiguous():
+        raise RuntimeError(f"moe_fp8_down_grouped: part must be a contiguous float32 tensor with >= {S * H} elements")
+    with torch.cuda.device(act.device):
+        rc = _lib.load().gptqhip_moe_fp8_down_grouped(_ptr(act), _ptr(weight_t), _ptr(rscale), _ptr(sorted_slots), _ptr(unit_expert),
+                                                      _ptr(num_units), _ptr(part), S // top_k, top_k, E, H, I, scale_mode, br, bc, _DT[act.dtype],
+                                                      _stream(act.device))
+    _lib.check(rc, "gptqhip_moe_fp8_down_grouped")
+    return part
 
 
 def dequant(qweight, qzeros, scales, g_idx, group_size: int, bits: int, out_dtype=None) -> torch.Tensor:

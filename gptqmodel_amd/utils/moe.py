@@ -50,8 +50,8 @@ def _is_moe_block(m) -> bool:
 def fuse_moe_experts(block: nn.Module, grouped_routing: Optional[bool] = None) -> bool:
     """Replace `block.experts` (a container of per-expert HIP GPTQ MLPs) by one HipMoeExperts, or (of per-expert HIP FP8 MLPs) by one
     HipFp8MoeExperts.  True when replaced; False -- with the reason in `block._gptqhip_moe_skipped` and the block untouched -- otherwise.
-    Never raises.  grouped_routing: the HipMoeExperts stand-in's `grouped_routing` attribute (the expert-grouped device-routed path beyond 16
-    tokens, which the FP8 stand-in does not have); None keeps its default (GPTQHIP_MOE_GROUPED=1 in the environment)."""
+    Never raises.  grouped_routing: the stand-in's `grouped_routing` attribute (the expert-grouped device-routed path beyond 16 tokens, int4
+    and FP8 alike); None keeps its default (GPTQHIP_MOE_GROUPED=1 in the environment)."""
     try:
         from ..nn_modules.moe import HipMoeExperts
         from ..nn_modules.moe_base import StackedMoeExperts
@@ -81,7 +81,7 @@ def fuse_moe_experts(block: nn.Module, grouped_routing: Optional[bool] = None) -
             fused = fused_cls.from_linears(gate, up, down)
         except NotImplementedError as e:
             return _decline(block, f"experts cannot share the stacked layout: {e}")
-        if grouped_routing is not None and fused_cls is HipMoeExperts:
+        if grouped_routing is not None:
             fused.grouped_routing = bool(grouped_routing)
         block.experts = fused
         if hasattr(block, "_gptqhip_moe_skipped"):

@@ -366,6 +366,33 @@ int gptqhip_moe_fp8_down(const void* act, const uint8_t* weight_t, const float* 
                          int32_t* status, int T, int top_k, int E, int H, int I, int scale_mode, int block_rows, int block_cols, int act_dtype,
                          gptqhip_stream_t stream);
 
+/* EXPERT-GROUPED FUSED FP8 MoE STAGES for any number of tokens (gptqmodel_amd/csrc/gptqhip_moe_fp8_grouped.hip): the two matrix stages of the
+ * expert-grouped pipeline on the stacked FP8 weights and reciprocal scales of the two ops above, between the format-agnostic
+ * gptqhip_moe_align and gptqhip_moe_combine:  align -> moe_fp8_gate_up_grouped -> moe_fp8_down_grouped -> combine.  Every 16-row unit of one
+ * expert streams the expert's weights once with all matrix-pipe rows carrying real tokens; four launches whose grids depend only on
+ * (T, top_k, E, shapes), nothing synchronises with the host, capturable at any supported T.
+ *   gptqhip_moe_fp8_gate_up_grouped  act[s, :I] for every slot s of a unit (sorted_slots / unit_expert / num_units as gptqhip_moe_align wrote
+ *            them), the rounding chain of gptqhip_moe_fp8_gate_up.  Rows of act whose slot is in no unit are left untouched.
+ *   gptqhip_moe_fp8_down_grouped     part[s, :H] = rscale * (act[s] . codes of W_down[ids[s]]): the UNROUNDED fp32 dot products with the
+ *            reciprocal scale already applied (per K block, or once to the reduced sum for tensor / row scales), float32 [S, H];
+ *            gptqhip_moe_combine then forms weights[t, j] * part[s] in slot order and rounds once -- the contract and the product order of
+ *            gptqhip_moe_fp8_down.
+ * No floating-point atomics; the rows of a unit never mix and the in-block split of K (contiguous chunk ranges over min(8 | 16, K / 128) waves)
+ * depends on the shape alone, so a token's output bits do not depend on what else is in the batch.  The K summation order differs from
+ * gptqhip_moe_fp8_gate_up / gptqhip_moe_fp8_down: same contract, not the same bits.  An id or slot gptqhip_moe_align would never produce
+ * dereferences nothing.  Supported (gptqhip_moe_fp8_grouped_supported, host logic, no GPU; everything else returns GPTQHIP_EINVAL with a message
+ * before any device access): the shape, scale-layout and dtype rules of gptqhip_moe_fp8_supported without its T <= 16 limit, and the routing
+ * limits of the grouped ops (T >= 1, 1 <= top_k <= 16, 1 <= E <= 512, T * top_k <= 65536).  x / act / weight_t / part must be 16-byte aligned;
+ * rscale and the sort buffers 4-byte aligned. */
+int gptqhip_moe_fp8_grouped_supported(int H, int I, int gate_up_block_cols, int down_scale_mode, int down_block_rows, int down_block_cols, int T,
+                                      int top_k, int E, int act_dtype);
+int gptqhip_moe_fp8_gate_up_grouped(const void* x, const uint8_t* weight_t, const float* rscale, const int32_t* sorted_slots,
+                                    const int32_t* unit_expert, const int32_t* num_units, void* act, int T, int top_k, int E, int H, int I,
+                                    int block_cols, int act_dtype, gptqhip_stream_t stream);
+int gptqhip_moe_fp8_down_grouped(const void* act, const uint8_t* weight_t, const float* rscale, const int32_t* sorted_slots,
+                                 const int32_t* unit_expert, const int32_t* num_units, float* part, int T, int top_k, int E, int H, int I,
+                                 int scale_mode, int block_rows, int block_cols, int act_dtype, gptqhip_stream_t stream);
+
 /* Quantise-and-pack on the device: weight fp32 [N,K] (nn.Linear layout), scales fp32 [G,N], zeros
  * int32 [G,N], g_idx int32 [K] (negative entries wrap by +G) -> checkpoint-layout qweight int32 [K*bits/32, N] and
  * qzeros int32 [G, N*bits/32].  q = clamp(rint((w + zero*scale)/scale), 0, maxq) in fp32, scale == 0 -> 1e-6:
