@@ -70,6 +70,12 @@ SIGNATURES = {
     "gptqhip_moe_fp8_grouped_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "gptqhip_moe_fp8_gate_up_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_moe_fp8_down_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gptqhip_fp4_supported": (_i, [_i, _i, _i, _i, _i]),
+    "gptqhip_fp4_tiled_bytes": (_sz, [_i, _i]),
+    "gptqhip_fp4_scale_bytes": (_sz, [_i, _i]),
+    "gptqhip_fp4_repack": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "gptqhip_fp4_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "gptqhip_fp4_dequant": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "gptqhip_pack_gptq": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "gptqhip_pack_gptq_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "gptqhip_gather_cols": (_i, [_vp, _vp, _vp, _i, _i, _vp]),

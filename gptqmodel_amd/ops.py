@@ -532,6 +532,107 @@ def fp8_dequant(weight_t: torch.Tensor, rscale: torch.Tensor, K: int, N: int, sc
     return out
 
 
+FP4_BLOCK = 16
+FP4_CVT = {"default": 0, "packed": 1, "f32": 2}
+
+
+def fp4_supported(M: int, K: int, N: int, block_size: int = FP4_BLOCK, dtype: torch.dtype = torch.float16) -> bool:
+    """True when gptqhip_fp4_gemm serves x [M, K] on an NVFP4 [N, K] weight (one e4m3 scale per `block_size` input features) with this
+    activation dtype -- gptqhip_fp4_supported, host logic, no GPU."""
+    return bool(_lib.load().gptqhip_fp4_supported(M, K, N, int(block_size), _DT.get(dtype, -1)))
+
+
+def _fp4_global_scale(global_scale: Optional[torch.Tensor], what: str) -> Optional[torch.Tensor]:
+    if global_scale is not None and (global_scale.dtype != torch.float32 or global_scale.numel() != 1):
+        raise RuntimeError(f"{what}: global_scale must be a float32 tensor of one element (or None = 1.0)")
+    return global_scale
+
+
+def _fp4_check_layout(what: str, weight_t: torch.Tensor, scale_t: torch.Tensor, K: int, N: int):
+    if weight_t.dtype != torch.uint8 or weight_t.numel() * 2 != K * N or scale_t.dtype != torch.uint8 or scale_t.numel() * FP4_BLOCK != K * N:
+        raise RuntimeError(f"{what}: weight_t must hold K * N / 2 = {K * N // 2} bytes and scale_t K * N / 16 = {K * N // 16} bytes (uint8)")
+
+
+def fp4_repack(weight: torch.Tensor, weight_scale: torch.Tensor, block_size: int = FP4_BLOCK):
+    """Checkpoint tensors (weight uint8 | float4_e2m1fn_x2 [N, K / 2], low nibble = even feature; weight_scale float8_e4m3fn | uint8
+    [N, K / 16]) -> (weight_t uint8 [K * N / 2], scale_t uint8 [K * N / 16]) in the MFMA-tile-major kernel layout.  One-time, on the device."""
+    lib = _lib.load()
+    _require_cuda(weight, weight_scale)
+    if weight.dim() != 2 or weight.element_size() != 1 or weight_scale.dim() != 2 or weight_scale.element_size() != 1:
+        raise RuntimeError(f"fp4_repack: weight and weight_scale must be 2-D one-byte tensors (got {weight.dtype} {tuple(weight.shape)}, "
+                           f"{weight_scale.dtype} {tuple(weight_scale.shape)})")
+    if weight_scale.dtype not in (torch.uint8, torch.float8_e4m3fn):
+        raise RuntimeError(f"fp4_repack: weight_scale must be float8_e4m3fn (or its uint8 view), got {weight_scale.dtype}")
+    N, K = weight.shape[0], weight.shape[1] * 2
+    if tuple(weight_scale.shape) != (N, K // max(int(block_size), 1)):
+        raise RuntimeError(f"fp4_repack: weight_scale shape {tuple(weight_scale.shape)} != {(N, K // max(int(block_size), 1))} "
+                           "(plain row-major; a swizzled scale layout is not supported)")
+    nbytes, sbytes = lib.gptqhip_fp4_tiled_bytes(K, N), lib.gptqhip_fp4_scale_bytes(K, N)
+    if nbytes == 0 or int(block_size) != FP4_BLOCK:
+        raise RuntimeError(f"fp4_repack: unsupported shape K={K} N={N} block size {block_size} (K % 128 == 0, N % 16 == 0, block size 16)")
+    w = weight.contiguous().view(torch.uint8)
+    s = weight_scale.contiguous().view(torch.uint8)
+    w_t = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    s_t = torch.empty(sbytes, dtype=torch.uint8, device=weight.device)
+    with torch.cuda.device(weight.device):
+        rc = lib.gptqhip_fp4_repack(_ptr(w), _ptr(s), _ptr(w_t), _ptr(s_t), K, N, int(block_size), _stream(weight.device))
+    _lib.check(rc, "gptqhip_fp4_repack")
+    return w_t, s_t
+
+
+def fp4_gemm(x: torch.Tensor, weight_t: torch.Tensor, scale_t: torch.Tensor, global_scale: Optional[torch.Tensor],
+             bias: Optional[torch.Tensor], N: int, block_size: int = FP4_BLOCK, out: Optional[torch.Tensor] = None,
+             cvt: str = "default") -> torch.Tensor:
+    """out[M, N] = x[M, K] @ W^T (+ bias) with W = code * block scale * global_scale: exact block-scaled weights on the matrix pipe, fp32
+    sums, the global scale and the bias on the accumulator, ONE rounding (gptqhip_fp4_gemm): the decode kernel up to 16 rows, the MFMA-tiled
+    general kernel above.  `global_scale`: a one-element float32 DEVICE tensor or None (1.0).  `cvt`: the conversion route (FP4_CVT)."""
+    lib = _lib.load()
+    if not (x.is_cuda and weight_t.is_cuda and scale_t.is_cuda and (bias is None or bias.is_cuda)
+            and (global_scale is None or global_scale.is_cuda)):
+        raise RuntimeError("gptqmodel_amd HIP ops need tensors on a ROCm device (got a CPU tensor); "
+                           "there is no CPU fallback")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise RuntimeError("fp4_gemm: x must be a contiguous [M,K] tensor")
+    adt = _DT.get(x.dtype)
+    if adt is None:
+        raise RuntimeError(f"fp4_gemm: unsupported activation dtype {x.dtype}")
+    if bias is not None and (bias.dtype != x.dtype or bias.numel() != N or not bias.is_contiguous()):
+        raise RuntimeError("fp4_gemm: bias must be a contiguous [N] tensor of the activation dtype")
+    M, K = x.shape
+    _fp4_check_layout("fp4_gemm", weight_t, scale_t, K, N)
+    _fp4_global_scale(global_scale, "fp4_gemm")
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.numel() != M * N or not out.is_contiguous():
+        raise RuntimeError("fp4_gemm: out must be a contiguous [M,N] tensor of the activation dtype")
+    if M == 0:
+        return out
+    with torch.cuda.device(x.device):
+        rc = lib.gptqhip_fp4_gemm(x.data_ptr(), weight_t.data_ptr(), scale_t.data_ptr(), 0 if global_scale is None else global_scale.data_ptr(),
+                                  0 if bias is None else bias.data_ptr(), out.data_ptr(), M, K, N, int(block_size), adt, FP4_CVT[cvt],
+                                  _stream_handle(_dev_index(x.device)))
+    if rc != 0:
+        _lib.check(rc, "gptqhip_fp4_gemm")
+    return out
+
+
+def fp4_dequant(weight_t: torch.Tensor, scale_t: torch.Tensor, global_scale: Optional[torch.Tensor], K: int, N: int,
+                block_size: int = FP4_BLOCK, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """[K, N] weights from the kernel layout in fp16 | bf16 | fp32, each element round(fp32(code * block scale) * global_scale), once."""
+    lib = _lib.load()
+    _require_cuda(weight_t, scale_t, global_scale)
+    if out_dtype not in _DT_OUT:
+        raise RuntimeError(f"fp4_dequant: unsupported output dtype {out_dtype}")
+    _fp4_check_layout("fp4_dequant", weight_t, scale_t, K, N)
+    _fp4_global_scale(global_scale, "fp4_dequant")
+    out = torch.empty((K, N), dtype=out_dtype, device=weight_t.device)
+    with torch.cuda.device(weight_t.device):
+        rc = lib.gptqhip_fp4_dequant(_ptr(weight_t), _ptr(scale_t), _ptr(global_scale), _ptr(out), K, N, int(block_size), _DT_OUT[out_dtype],
+                                     _stream(weight_t.device))
+    _lib.check(rc, "gptqhip_fp4_dequant")
+    return out
+
+
 def moe_fp8_supported(H: int, I: int, gate_up_block_cols: int = 0, down_scale_mode: int = FP8_SCALE_ROW, down_block_size=None, T: int = 1,
                       top_k: int = 1, dtype: torch.dtype = torch.float16) -> bool:
     """True when the fused FP8 MoE decode ops (gptqhip_moe_fp8_gate_up / gptqhip_moe_fp8_down) serve experts with hidden size H and intermediate

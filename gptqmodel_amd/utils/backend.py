@@ -1,7 +1,7 @@
 """BACKEND selector values.  Mirrors gptqmodel/utils/backend.py:10-87 for the members that matter here and
 adds the members this backend introduces (INTEGRATION.md shows the two-line upstream patch for the first two):
 
-    GPTQ_HIP = "gptq_hip"     AWQ_HIP = "awq_hip"     FP8_HIP = "fp8_hip"      (+ method-generic legacy-style alias HIP = "hip")
+    GPTQ_HIP = "gptq_hip"     AWQ_HIP = "awq_hip"     FP8_HIP = "fp8_hip"     FP4_HIP = "fp4_hip"      (+ method-generic legacy-style alias HIP = "hip")
 """
 from __future__ import annotations
 
@@ -16,6 +16,7 @@ class BACKEND(str, Enum):
     GPTQ_HIP = "gptq_hip"
     AWQ_HIP = "awq_hip"
     FP8_HIP = "fp8_hip"
+    FP4_HIP = "fp4_hip"
     HIP = "hip"  # generic alias resolved per quant method, like upstream's TORCH/MARLIN legacy names
     # upstream names kept so that saved configs naming them fail with a clear message instead of a KeyError
     GPTQ_TORCH = "gptq_torch"
@@ -28,6 +29,7 @@ _LEGACY_BACKEND_BY_METHOD = {
     "gptq": {BACKEND.HIP: BACKEND.GPTQ_HIP, BACKEND.TORCH: BACKEND.GPTQ_TORCH},
     "awq": {BACKEND.HIP: BACKEND.AWQ_HIP, BACKEND.TORCH: BACKEND.AWQ_TORCH, BACKEND.TORCH_AWQ: BACKEND.AWQ_TORCH},
     "fp8": {BACKEND.HIP: BACKEND.FP8_HIP},
+    "nvfp4": {BACKEND.HIP: BACKEND.FP4_HIP},
 }
 
 

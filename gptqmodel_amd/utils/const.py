@@ -3,7 +3,7 @@ checkpoints' quantize_config.json strings parse identically.
 
 Reference definitions: DEVICE / PLATFORM  gptqmodel/models/_const.py:41-84,
 FORMAT / METHOD  gptqmodel/quantization/config.py:106-141.
-Only the members relevant to the GPTQ/AWQ int4/int8 and FP8 weight-only hot paths are listed; the HIP backend is
+Only the members relevant to the GPTQ/AWQ int4/int8, FP8 and NVFP4 weight-only hot paths are listed; the HIP backend is
 `DEVICE.ROCM`-only by construction.
 """
 from __future__ import annotations
@@ -38,12 +38,16 @@ class FORMAT(str, Enum):
     GPTQ_P = "gptq_p"    # planar (split-plane) words, qzeros hold zero: what 5 / 6 / 7-bit checkpoints declare, optional for 3 bits
     GEMM = "gemm"        # AWQ GEMM layout
     FP8 = "fp8"          # float8 weight-only checkpoints: `weight` fp8 [out, in] + `weight_scale_inv` fp32
+    # this package's own name: the reference has only WeightOnlyMethod.NVFP4 (quantization/config.py:177) and detects the format from the
+    # tensors (models/base.py:2099-2142): `weight` e2m1 x 2 per byte [out, in / 2] + `weight_scale` e4m3 [out, in / 16] + `weight_scale_2` fp32
+    NVFP4 = "nvfp4"
 
 
 class METHOD(str, Enum):
     GPTQ = "gptq"
     AWQ = "awq"
     FP8 = "fp8"
+    NVFP4 = "nvfp4"      # this package's own name, like FORMAT.NVFP4 (the reference: WeightOnlyMethod.NVFP4, quantization/config.py:177)
 
 
 IS_ROCM = bool(getattr(torch.version, "hip", None))

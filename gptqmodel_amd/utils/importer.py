@@ -33,7 +33,7 @@ def _supports_pack_api(cls: Type[BaseQuantLinear]) -> bool:
 
 
 def _import_all_qlinear_kernels() -> None:
-    from ..nn_modules.qlinear import hip_awq, hip_fp8, hip_gptq  # noqa: F401
+    from ..nn_modules.qlinear import hip_awq, hip_fp4, hip_fp8, hip_gptq  # noqa: F401
 
 
 def iter_quant_linear_kernels() -> List[Type[BaseQuantLinear]]:

@@ -3,7 +3,8 @@
 `fuse_moe_experts(block)` recognises a sparse-MoE block whose `experts` is a container of per-expert MLP modules -- `gate_proj` / `up_proj` /
 `down_proj`, or Mixtral's `w1` / `w3` / `w2` -- all of them adapter-free 4-bit HIP GPTQ linears of equal shapes, group size and dtype without
 act-order, and replaces `block.experts` by one HipMoeExperts.  A block whose projections are ALL HipFp8Linear (float8_e4m3fn, one scale layout
-for gate / up and one for down) gets one HipFp8MoeExperts the same way; a mix of FP8 and other projections is declined.  The stand-in serves
+for gate / up and one for down) gets one HipFp8MoeExperts the same way; a mix of FP8 and other projections is declined, and so is a block
+with NVFP4 projections (HipFp4Linear: no stacked form yet).  The stand-in serves
 the call the block's forward makes under the installed transformers release, `self.experts(hidden_states, top_k_index, top_k_weights)`; a bare
 nn.ModuleList has no such call (the block's own forward indexes it) and is left alone.  Anything not recognised is left untouched with the
 reason recorded on the block (`block._gptqhip_moe_skipped`); the helper never raises.  `auto_fuse_moe(model)` applies it to every such block
@@ -74,6 +75,8 @@ def fuse_moe_experts(block: nn.Module, grouped_routing: Optional[bool] = None) -
                 return _decline(block, "expert activation is not SiLU")
         gate, up, down = ([getattr(e, n) for e in mods] for n in names)
         kinds = {getattr(m, "QUANT_TYPE", "") for m in gate + up + down}
+        if "hip_fp4" in kinds:
+            return _decline(block, "NVFP4 experts (HipFp4Linear) have no stacked fused form: each projection keeps its own launch")
         if "hip_fp8" in kinds and len(kinds) > 1:
             return _decline(block, f"experts mix FP8 and other projections ({', '.join(sorted(str(k) or 'unquantised' for k in kinds))})")
         fused_cls = HipFp8MoeExperts if kinds == {"hip_fp8"} else HipMoeExperts

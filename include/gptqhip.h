@@ -393,6 +393,44 @@ int gptqhip_moe_fp8_down_grouped(const void* act, const uint8_t* weight_t, const
                                  const int32_t* unit_expert, const int32_t* num_units, float* part, int T, int top_k, int E, int H, int I,
                                  int scale_mode, int block_rows, int block_cols, int act_dtype, gptqhip_stream_t stream);
 
+/* NVFP4 WEIGHT-ONLY LINEAR, W4A16 (gptqmodel_amd/csrc/gptqhip_fp4.hip): e2m1 weights with one float8_e4m3fn scale per 16 input features and one fp32
+ * global scale, fp16 | bf16 activations (never quantised), fp32 accumulation.  Serves the checkpoints the reference rebuilds as TorchFP4Linear
+ * (gptqmodel/nn_modules/qlinear/fp4.py:19, models/base.py:2099-2142), METHOD.NVFP4 / FORMAT.NVFP4.  Additive: GPTQHIP_ABI_VERSION stays 21.
+ *   Semantics: W[n, k] = code[n, k] * weight_scale[n, k / 16] * global_scale.  weight uint8 [N, K / 2]: feature 2 b is the LOW nibble of byte b
+ *            (gptqmodel_ext/floatx_cpu.cpp:1998-2003), code `s e1 e0 m` = +-{0, 0.5, 1, 1.5, 2, 3, 4, 6} (floatx_cpu.cpp:153-156); weight_scale
+ *            float8_e4m3fn bytes [N, K / 16], plain row-major; global_scale a DEVICE pointer to one float (ModelOpt's weight_scale_2), NULL = 1.0 --
+ *            a pointer so that nothing synchronises with the host and a later stacked-expert form can index it.
+ *   Numerics: y[m, n] = round_act( s2 * sum_k x[m, k] * (code[n, k] * s_blk[n, k / 16]) + bias[n] ).  Every product code * s_blk is exact in fp16 and
+ *            in bf16 (at most 6 significant bits, 2^-10 .. 2688), so the block-scaled weights enter the f16 / bf16 matrix pipe exactly and no
+ *            per-block accumulator flush exists; sums are fp32; s2 and the bias are applied to the fp32 accumulator; ONE rounding.  Deliberately
+ *            not the reference's chain (quantization/dtype.py:303-340: table value and effective scale cast to the activation dtype, the product
+ *            rounded, then the matmul's and the bias add's roundings): the choice of decode form 5 and gptqhip_fp8_gemm, held to the same bar
+ *            (tests/test_gpu_fp4.py).
+ *   NaN scale bytes (0x7f, 0xff): undefined.  Every other scale byte (+-0, subnormals, negative values) is defined.  The sign of a zero output is
+ *            not part of the contract.
+ *   Supported (gptqhip_fp4_supported, host logic, no GPU; everything else returns GPTQHIP_EINVAL with a message before any device access):
+ *            block_size 16; act_dtype fp16 | bf16; K % 128 == 0; N % 16 == 0; 0 <= M <= 65535 * 64.
+ *   gptqhip_fp4_tiled_bytes(K, N) / gptqhip_fp4_scale_bytes(K, N)  bytes of the two kernel-layout arrays (K * N / 2, K * N / 16; 0 = unsupported shape).
+ *   gptqhip_fp4_repack    post_init: weight / weight_scale in the checkpoint layout -> weight_t / scale_t in the MFMA-tile-major layout (1 KiB of
+ *            codes + 128 B of scales per (16-column tile, 128-row chunk), gptqhip_fp4.hip).  Not in place.
+ *   gptqhip_fp4_gemm      out[M, N] = x[M, K] @ W^T (+ bias).  x / out / bias in act_dtype; all tensors 16-byte aligned.  1 <= M <= 16: the decode kernel
+ *            (one launch, grid a function of (K, N) only: capturable; bits independent of the run and of the other rows); M >= 17: the MFMA-tiled
+ *            general kernel (no workspace); M == 0: a no-op success.  flags: GPTQHIP_FP4_CVT_* picks the conversion route (all give the same bits).
+ *   gptqhip_fp4_dequant   out[K, N] in out_dtype (fp16 | bf16 | GPTQHIP_FP32) from the kernel layout, each element round(fp32(code * s_blk) * s2), once. */
+#define GPTQHIP_FP4_CVT_DEFAULT 0     /* fp16: packed, bf16: f32 (profiles/r15_fp4_linear.txt)                                  */
+#define GPTQHIP_FP4_CVT_PACKED 1      /* v_cvt_scalef32_pk_{f16,bf16}_fp4, then the block scale by a packed multiply            */
+#define GPTQHIP_FP4_CVT_F32 2         /* v_cvt_scalef32_pk_f32_fp4, v_pk_mul_f32 by the block scale, a packed fp32 -> 16-bit convert */
+#define GPTQHIP_FP4_CVT_MASK 3
+int gptqhip_fp4_supported(int M, int K, int N, int block_size, int act_dtype);
+size_t gptqhip_fp4_tiled_bytes(int K, int N);
+size_t gptqhip_fp4_scale_bytes(int K, int N);
+int gptqhip_fp4_repack(const uint8_t* weight, const uint8_t* weight_scale, uint8_t* weight_t, uint8_t* scale_t, int K, int N, int block_size,
+                       gptqhip_stream_t stream);
+int gptqhip_fp4_gemm(const void* x, const uint8_t* weight_t, const uint8_t* scale_t, const float* global_scale, const void* bias, void* out, int M,
+                     int K, int N, int block_size, int act_dtype, int flags, gptqhip_stream_t stream);
+int gptqhip_fp4_dequant(const uint8_t* weight_t, const uint8_t* scale_t, const float* global_scale, void* out, int K, int N, int block_size,
+                        int out_dtype, gptqhip_stream_t stream);
+
 /* Quantise-and-pack on the device: weight fp32 [N,K] (nn.Linear layout), scales fp32 [G,N], zeros
  * int32 [G,N], g_idx int32 [K] (negative entries wrap by +G) -> checkpoint-layout qweight int32 [K*bits/32, N] and
  * qzeros int32 [G, N*bits/32].  q = clamp(rint((w + zero*scale)/scale), 0, maxq) in fp32, scale == 0 -> 1e-6:
