@@ -259,7 +259,10 @@ __global__ __launch_bounds__(256) void fp4_dequant_kernel(Fp4Params p) {
     const uint32_t nib = (p.wt[fp4_tiled_offset(k, n, p.chunks)] >> (4 * (k & 1))) & 0xfu;
     const float code = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(nib, 1.0f, 0)[0];
     const float sb = __builtin_amdgcn_cvt_f32_fp8((int)p.st[fp4_scale_offset(k, n, p.chunks)], 0);
-    const float v = (code * sb) * (p.gs ? p.gs[0] : 1.f);   // the first product is exact, the second is rounded to fp32
+    float v = (code * sb) * (p.gs ? p.gs[0] : 1.f);   // the first product is exact, the second is rounded to fp32
+    // ... and held in a register of its own: hipcc would fold it into the fp16 conversion (v_fma_mixlo_f16), which rounds the exact product to
+    // fp16, one ulp off round(fp32 product) wherever the fp32 product is an fp16 tie (gptqhip_fp8.hip: fp8_dequant_kernel)
+    asm volatile("" : "+v"(v));
     if constexpr (OUT == 2) {
         reinterpret_cast<float*>(p.out)[idx] = v;
     } else {

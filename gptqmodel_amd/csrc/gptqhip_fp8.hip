@@ -229,11 +229,11 @@ __global__ __launch_bounds__(256) void fp8_dequant_kernel(Fp8Params p) {
     const int k = (int)(idx / p.N), n = (int)(idx % p.N);
     const float code = __builtin_amdgcn_cvt_f32_fp8((int)p.wt[fp8_tiled_offset(k, n, p.chunks)], 0);
     const float r = p.mode == kScaleTensor ? p.rs[0] : p.mode == kScaleRow ? p.rs[n] : p.rs[(size_t)(n / p.br) * p.kbn + k / p.bc];
-    // code * r with IEEE's sign of a zero product: for fptrunc(a * b) hipcc selects v_fma_mixlo_f16 with a +0 addend, which turns the -0 of
-    // code 0x80 into +0; an fma with an opaque -0 addend keeps the sign and changes nothing else (the trick of gptqhip_aux.hip)
-    float nz = -0.f;
-    asm volatile("" : "+v"(nz));
-    const float v = __builtin_fmaf(code, r, nz);
+    // The fp32 product is held in a register of its own.  Left to itself hipcc folds the multiply into the fp16 conversion (v_fma_mixlo_f16,
+    // with a +0 addend for a plain product), which rounds the EXACT product to fp16: one ulp off round(fp32 product) wherever the fp32 product is
+    // an fp16 tie, so the fp16 output was not the fp32 output rounded; the +0 addend also turned the -0 of code 0x80 into +0.
+    float v = code * r;
+    asm volatile("" : "+v"(v));
     if constexpr (OUT == 2) {
         reinterpret_cast<float*>(p.out)[idx] = v;
     } else {

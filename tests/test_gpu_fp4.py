@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import fp4_oracle as F4
+import linear_wave_model as LM
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -155,6 +156,25 @@ def test_every_code_times_every_scale_through_both_kernels_and_the_dequant(s2):
                 assert torch.equal(ops.fp4_gemm(x, w_t, s_t, gs, None, N, cvt=cvt), base), (act, M, cvt)
 
 
+def test_dequant_rounds_the_fp32_product_where_it_is_an_fp16_tie():
+    """s2 = 0.014662: for some of the code x scale products the fp32 product with s2 lies exactly between two fp16 values and the exact product
+    does not, so rounding the exact product -- what a multiply folded into the fp16 conversion does -- and rounding the fp32 product differ by
+    one ulp.  The dequant's contract is round(fp32(code * s_blk) * s2): its fp16 and bf16 outputs are its fp32 output rounded."""
+    from gptqmodel_amd import ops
+    N, K = 256, 128
+    codes, scale = every_code_layer()
+    s2 = np.float32(0.014662)
+    blk = F4.block_weights64(codes, scale)
+    assert ((blk * np.float64(s2)).astype(np.float16) != (blk.astype(np.float32) * s2).astype(np.float16)).any()   # the premise (numpy rounds once)
+    w_t, s_t = repacked(codes, scale)
+    gs = scalar(float(s2))
+    w32 = ops.fp4_dequant(w_t, s_t, gs, K, N, out_dtype=torch.float32)
+    assert np.array_equal(host(w32), F4.kernel_w(codes, scale, s2).T.astype(np.float64))
+    for act in ("fp16", "bf16"):
+        got = ops.fp4_dequant(w_t, s_t, gs, K, N, out_dtype=TDT[act])
+        assert torch.equal(got, w32.to(TDT[act])), (act, int((got != w32.to(TDT[act])).sum()))
+
+
 # ---- placement ----------------------------------------------------------------------------------------------------------------------------------
 def test_nibble_and_block_placement():
     """A weight that is zero but for one code at (n, k) must show that code at exactly [k, n] of the dequant, whatever nibble, dword, lane,
@@ -181,6 +201,20 @@ def test_nibble_and_block_placement():
         want[16 * blk:16 * blk + 16, n] = 3.25
         assert np.array_equal(got, want), (n, blk)
         y = host(ops.fp4_gemm(dev(np.ones((2, K)), "fp16"), w_t, s_t, None, None, N))
+        assert np.array_equal(y, np.tile(want.sum(axis=0), (2, 1))), (n, blk)
+    # beyond chunk 1: K = 4224, where wave 7 of the decode kernel runs 4 + 1 chunks.  One block in the chunk of its second trip (the one its
+    # surplus loads repeat), one in a first-trip chunk at u = 3 of wave 7 and of wave 0, one mid-round (linear_wave_model.FP4_DEEP_PLACEMENT)
+    K = 4224
+    codes = np.full((N, K), 0x02, np.uint8)
+    for n, blk in LM.FP4_DEEP_PLACEMENT:
+        scale = np.full((N, K // 16), one, np.uint8)
+        scale[n, blk] = 0x45
+        w_t, s_t = repacked(codes, scale)
+        got = host(ops.fp4_dequant(w_t, s_t, None, K, N))
+        want = np.ones((K, N))
+        want[16 * blk:16 * blk + 16, n] = 3.25
+        assert np.array_equal(got, want), (n, blk)
+        y = host(ops.fp4_gemm(dev(np.ones((2, K)), "fp16"), w_t, s_t, None, None, N))          # 4224 and 4260: exact in fp16
         assert np.array_equal(y, np.tile(want.sum(axis=0), (2, 1))), (n, blk)
 
 

@@ -157,6 +157,26 @@ def test_every_code_through_both_kernels_and_the_dequant(method, block, pow2):
                        ops.fp8_gemm(xb, w_t, rs.reshape(-1), None, N, mode_of(method), block))
 
 
+def test_dequant_rounds_the_fp32_product_where_it_is_an_fp16_tie():
+    """scale_inv = 669.26: for some codes the fp32 product code * fp32(1 / scale_inv) lies exactly between two fp16 values and the exact
+    product does not, so rounding the exact product -- what a multiply folded into the fp16 conversion does -- and rounding the fp32 product
+    differ by one ulp.  The dequant's contract is the fp32 product, rounded once: its fp16 and bf16 outputs are its fp32 output rounded."""
+    from gptqmodel_amd import ops
+    N, K = 48, 256
+    codes, _ = every_code_layer(N, False, "tensor", None)
+    scale_inv = np.float32(669.26)
+    r = np.float32(1.0) / scale_inv
+    exact, prod = F.E4M3[F.FINITE_CODES] * np.float64(r), F.E4M3[F.FINITE_CODES].astype(np.float32) * r
+    assert (exact.astype(np.float16) != prod.astype(np.float16)).any()          # the premise (numpy rounds a float64 to fp16 once)
+    w_t, rs = repacked(codes, scale_inv, "tensor", None)
+    w32 = ops.fp8_dequant(w_t, rs.reshape(-1), K, N, mode_of("tensor"), None, out_dtype=torch.float32)
+    assert np.array_equal(host(w32), F.kernel_w(codes, scale_inv).T.astype(np.float64))
+    for act in ("fp16", "bf16"):
+        got = ops.fp8_dequant(w_t, rs.reshape(-1), K, N, mode_of("tensor"), None, out_dtype=TDT[act])
+        assert torch.equal(got, w32.to(TDT[act])), (act, int((got != w32.to(TDT[act])).sum()))
+        assert torch.equal(torch.signbit(got), torch.signbit(w32))
+
+
 # ---- dynamic range --------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M", [3, 19])
 @pytest.mark.parametrize("act", ["fp16", "bf16"])
